@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Training-throughput benchmark: KITTI 192x640 multi-frame self-supervised.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
 
 Workload (BASELINE.json configs[1]): SelfSupModelMF +
@@ -12,8 +12,15 @@ that shape (smooth random textures, shifted context frames), random init.
 A step = zero_grad -> forward -> loss -> backward -> RCCL all-reduce -> Adam.
 
 Prints ONE JSON line on rank 0; `value` = images/s over all ranks (weak
-scaling: per-GPU batch fixed).  Also reports the roofline of the dominant
-kernel (HIP events) and the CPU-oracle baseline on this host's cores.
+scaling: per-GPU batch fixed).  A plain run sets up, warms up, times the K
+steps and prints the line.  --full adds the measurements that take runs of
+their own: the roofline of the dominant kernels (HIP events) and the
+CPU-oracle baseline on this host's cores.  --dump-outputs DIR writes what the
+last timed step returned and left behind (loss, metrics, gradients, updated
+parameters) as DIR/<name>.npy.  The inputs depend only on the arguments, and
+the last timed step starts again from the state before the first step (see
+main), so two runs agree to rounding and two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -396,6 +403,55 @@ def _cpu_model():
     return "unknown"
 
 
+# ----------------------------------------------------------------------------- outputs
+DUMP_MAX_ELEMS = 4 << 20    # per array: 16 MB of float32, so a dump stays well under 64 MB
+
+
+def _dump_array(t):
+    """float32 host array of a tensor; a flat tensor beyond DUMP_MAX_ELEMS is
+    sampled at fixed, seeded positions (the same for every run and build)."""
+    t = t.detach().to(torch.float32).cpu()
+    if t.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(2024)
+        idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+        t = t.reshape(-1)[idx]
+    return t.contiguous().numpy()
+
+
+def snapshot_state(trainer):
+    """The training state before the first step -- flat parameters, Adam moments
+    and step counter, the model's buffers -- as (live tensors, copies)."""
+    st = trainer.optimizer.state["flat"]
+    live = [trainer.flat_params, st["exp_avg"], st["exp_avg_sq"], st["step"]] + list(trainer.model.buffers())
+    return live, [t.clone() for t in live]
+
+
+def restore_state(snap):
+    """Copy a snapshot_state() back in place (a captured graph holds the
+    addresses of the live tensors)."""
+    live, saved = snap
+    with torch.no_grad():
+        for t, s in zip(live, saved):
+            t.copy_(s)
+
+
+def dump_outputs(out_dir, loss, metrics, trainer):
+    """What the last timed step handed back and left behind, as <name>.npy: the
+    loss and the metrics that step() returned, the flat gradient it reduced
+    and the flat parameters after its Adam update."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {} if loss is None else {"loss": loss}
+    for k, v in sorted(metrics.items()):
+        if torch.is_tensor(v):
+            arrays["metrics_" + k.replace("/", "_")] = v
+    arrays["grads"] = trainer.grads.flat
+    arrays["params"] = trainer.flat_params
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), _dump_array(t))
+    return sorted(arrays)
+
+
 # ----------------------------------------------------------------------------- launcher
 def _free_port():
     import socket
@@ -444,8 +500,15 @@ def main():
                     help="BASELINE.json config (default: the metric's, configs[1])")
     ap.add_argument("--batch", type=int, default=None, help="target frames per GPU (default: the workload's)")
     ap.add_argument("--flip-prob", type=float, default=0.5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned and left behind (loss, "
+                         "metrics, flat gradient, flat parameters) as DIR/<name>.npy (float32; arrays beyond "
+                         "4 Mi elements as a fixed seeded sample); rank 0 only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the kernel rooflines (HIP-event loops of their "
+                         "own) and the CPU-oracle baseline, and add them to the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the rooflines")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture of the step")
     ap.add_argument("--pipeline", choices=("resident", "gpu"), default="resident",
                     help="resident: float batches already in HBM (the metric's contract); gpu: every step "
@@ -489,6 +552,12 @@ def main():
     model = build_model(device, args.flip_prob)
     model.seed(42 + rank)
     trainer = DataParallelTrainer(model, lr=2e-4, bucket_mb=25.0, capturable=not args.eager)
+    # The warp-cost backward accumulates with atomic adds: the feature encoder's
+    # gradient differs by 1e-6 relative from process to process, and training from
+    # a random init amplifies that from step to step (losses 3 % apart after 25
+    # steps).  The last timed step therefore starts again from the state before
+    # the first one, so that what it computes depends on the arguments alone.
+    initial = snapshot_state(trainer)
     batches = [make_batch(args.batch, 1000 * rank + i, device) for i in range(4)]
     mode, stepper = "eager", None
     if not args.eager:
@@ -516,16 +585,20 @@ def main():
             b["intrinsics"].copy_(b["_K0"])
         return trainer.step(b)
 
+    loss = None
     for i in range(args.warmup):
         loss, _ = run(i)
-    if not torch.isfinite(loss).all():
+    if loss is not None and not torch.isfinite(loss).all():
         raise RuntimeError(f"non-finite loss in warmup: {loss}")
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    metrics = {}
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, _ = run(i)
+        if i == args.steps - 1:
+            restore_state(initial)
+        loss, metrics = run(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -554,9 +627,11 @@ def main():
                                 if getattr(stepper, "in_graph", False) else
                                 "all-reduce after each graph replay" if stepper is not None else
                                 "bucketed all-reduce from backward hooks (eager)")},
-        "final_loss": round(float(loss), 6),
+        "final_loss": round(float(loss), 6) if loss is not None else None,
     }
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, loss, metrics, trainer)
+    if rank == 0 and args.full and not args.no_roofline:
         result["roofline"] = roofline_conv(device, args.roofline_iters, TRAFFIC_FILE)
         if WL["kind"] == "selfsup":
             result["roofline_photometric"] = roofline_photometric(args.batch, device)
@@ -564,7 +639,7 @@ def main():
             result["roofline_supervised"] = roofline_supervised(args.batch, device)
         if args.workload == "kitti_selfsup":
             result["roofline_plane_sweep"] = roofline_plane_sweep(device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(model)
     if rank == 0:
         print(json.dumps(result), flush=True)

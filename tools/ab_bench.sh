@@ -8,7 +8,7 @@ for r in $(seq 1 "$ROUNDS"); do
   for v in "$@"; do
     tag=$(echo "$v" | tr -c 'A-Za-z0-9=_\n' '_' | tr '=' '-')
     if [ "$v" = base ]; then envs=""; else envs="$v"; fi
-    env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline \
+    env $envs timeout -k 10 300 python bench.py --steps 20 --warmup 5 \
       > "$OUT/bench_${tag}_$r.log" 2>&1 || { echo "variant $v failed"; exit 1; }
     echo "$v $r: $(grep -o '"ms_per_step": [0-9.]*' "$OUT/bench_${tag}_$r.log")"
   done

@@ -28,15 +28,15 @@ for step in "$@"; do
     tests) run pytest_gpu 1100 python -u -m pytest tests -m gpu -x -v --timeout=300 --timeout-method=thread -p no:cacheprovider ;;
     testsall) run pytest_gpu 1100 python -u -m pytest tests -m gpu -v --timeout=300 --timeout-method=thread -p no:cacheprovider ;;
     testsm) rm -f "$OUT/parity_margins.jsonl"; run pytest_gpu 1100 env DRO_PARITY_LOG="$OUT/parity_margins.jsonl" python -u -m pytest tests -m gpu -v --durations=15 --timeout=300 --timeout-method=thread -p no:cacheprovider ;;
-    bench) run bench 900 python bench.py --steps 20 --warmup 5 ;;
-    benchq) run bench 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ;;
-    benchab) run bench_a 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline ;;
-    benche) run bench_eager 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --eager ;;
-    benchms) run bench_miopen_strided 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --miopen-strided-convs ;;
-    benchpipe) run bench_pipeline 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline --pipeline gpu ;;
-    dp2) run bench_dp2_gloo_onegpu 600 env DRO_DIST_BACKEND=gloo DRO_BENCH_DEVICE=0 python bench.py --gpus 2 --steps 10 --warmup 3 --no-roofline ;;
-    prof) run rocprof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline ;;
-    profms) run rocprof_ms 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profms" -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --miopen-strided-convs ;;
+    bench) run bench 900 python bench.py --steps 20 --warmup 5 --full ;;
+    benchq) run bench 600 python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline ;;
+    benchab) run bench_a 600 python bench.py --steps 20 --warmup 5 ;;
+    benche) run bench_eager 600 python bench.py --steps 10 --warmup 3 --eager ;;
+    benchms) run bench_miopen_strided 600 python bench.py --steps 20 --warmup 5 --miopen-strided-convs ;;
+    benchpipe) run bench_pipeline 600 python bench.py --steps 20 --warmup 5 --pipeline gpu ;;
+    dp2) run bench_dp2_gloo_onegpu 600 env DRO_DIST_BACKEND=gloo DRO_BENCH_DEVICE=0 python bench.py --gpus 2 --steps 10 --warmup 3 ;;
+    prof) run rocprof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py --steps 5 --warmup 2 ;;
+    profms) run rocprof_ms 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profms" -o run -- python bench.py --steps 5 --warmup 2 --miopen-strided-convs ;;
     roof) run roofline_stats 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/roof" -o run -- python bench.py --roofline-only ;;
     roofonly) run roofonly 300 python bench.py --roofline-only ;;
     pmc) run pmc_fetch 600 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python bench.py --roofline-only &&
@@ -50,9 +50,9 @@ for step in "$@"; do
          run croof_table 60 python tools/conv_roofline.py table "$OUT/croof" --pmc-dirs "$OUT/croof_fetch" "$OUT/croof_write" "$OUT/croof_mfma" ;;
     tl) run step_timeline 300 python tools/step_timeline.py ;;
     photo) run photo_stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/photo" -o run -- python tools/bench_photo.py --iters 20 ;;
-    w:*) wl=${step#w:}; run "bench_$wl" 900 python bench.py --workload "$wl" --steps 10 --warmup 3 ;;
+    w:*) wl=${step#w:}; run "bench_$wl" 900 python bench.py --workload "$wl" --steps 10 --warmup 3 --full ;;
     envr:*) kv=${step#envr:}; run "roof_${kv%%=*}_${kv#*=}" 300 env "$kv" python bench.py --roofline-only ;;
-    envb:*) kv=${step#envb:}; run "bench_${kv%%=*}" 600 env "$kv" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-roofline ;;
+    envb:*) kv=${step#envb:}; run "bench_${kv%%=*}" 600 env "$kv" python bench.py --steps 20 --warmup 5 ;;
     k:*) kk=${step#k:}; run "pytest_k_${kk//[^a-zA-Z0-9]/_}" 900 python -u -m pytest tests -m gpu -v --timeout=300 --timeout-method=thread -p no:cacheprovider -k "$kk" ;;
     ms:*) kk=${step#ms:}; run "pytest_ms_${kk//[^a-zA-Z0-9]/_}" 900 env DRO_NATIVE_STRIDED=0 python -u -m pytest tests -m gpu -v --timeout=300 --timeout-method=thread -p no:cacheprovider -k "$kk" ;;
     t:*) f=${step#t:}; run "pytest_$(basename "$f" .py)" 900 python -u -m pytest "$f" -m gpu -v --timeout=300 --timeout-method=thread -p no:cacheprovider ;;
