@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -47,6 +48,7 @@
 
 #include "conv_common.hpp"
 #include "dro_common.hpp"
+#include "wgrad_group_plan.hpp"
 
 namespace dro {
 
@@ -1263,56 +1265,61 @@ struct HaloShapeW2 {
   static_assert(NJ <= 2 && TW % 2 == 0, "halo shape");
 };
 
-template <int KH, int KW, int GACT, bool MULTI, int TG>
-__global__ __launch_bounds__(512) void wgrad2_kernel(typename WgParam<MULTI>::T P) {
+// What one block of the weight gradient works on, block-uniform: its weight's
+// geometry, its (o, c) tile and run of pixel tiles, where its partials go, and
+// where its uses are found -- pointers (one use) or, with a use table, the
+// kernel-argument byte offsets of the weight's first use slot.
+struct WgBlock {
+  int H, W, Cin, Cout, cb1, cb2, cb3;
+  int tiles_x, tiles_img, use_tiles;
+  int o0, c0, tg, tbeg, tend;   // pixel tiles tfirst + tl * tstep, tl in [tbeg, tend)
+  int tfirst, tstep;
+  bool do_bias;
+  float galpha;
+  float* wpart;           // this split's [T][Cout][Cin]
+  float* bpart;           // this split's [Cout]
+  const float* G;
+  const float* gy;
+  KSlice srcs;
+  unsigned uG, uy, usrc;
+};
+
+template <int KH, int KW, int GACT, bool TABLE, int TG>
+__device__ __forceinline__ void wgrad2_block(const WgBlock& k) {
   static_assert(TG == 1 || (TG == 3 && KH == 3 && KW == 3), "tap groups: 3x3 rows");
-  const IgArgs& a = WgParam<MULTI>::ig(P);
   using S = HaloShapeW2<KH, KW, TG>;
   constexpr int T = S::T, TH = S::TH, TW = S::TW, HWd = S::HWd, HALO = S::HALO, HPAD = S::HPAD;
-  constexpr int NJ = S::NJ, BC = S::BC, GPAD = S::GPAD, STAGE = S::STAGE, TPW = S::TPW;
+  constexpr int NJ = S::NJ, GPAD = S::GPAD, STAGE = S::STAGE, TPW = S::TPW;
   constexpr bool TAPSPLIT = S::TAPSPLIT;
   constexpr int PH = KH / 2, PW = KW / 2;
   __shared__ float smem[S::LDS];
-  const int cb1 = a.cbase[1], cb2 = a.cbase[2], cb3 = a.cbase[3];
-  const int H = a.g.H, W = a.g.W, Cin = a.g.Cin, Cout = a.g.Cout;
+  const int cb1 = k.cb1, cb2 = k.cb2, cb3 = k.cb3;
+  const int H = k.H, W = k.W, Cin = k.Cin, Cout = k.Cout;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // 0..7
-  const int noc = a.otiles * ((Cin + BC - 1) / BC);
-  // XCD-aware block order: the blocks of consecutive splits (adjacent pixel
-  // runs: their halo rows share cache lines) and the channel tiles of one split
-  // (they stage the same G / X tiles) land on the same XCD, i.e. the same L2
-  const int nbx = (int)gridDim.x;
-  const int lin = xcd_remap((int)(blockIdx.x + blockIdx.y * gridDim.x), (int)(gridDim.x * gridDim.y));
-  const int bx = lin % nbx, by = lin / nbx;
-  const int tg = TG == 1 ? 0 : bx / noc;    // kernel row of this block (TG == 3)
-  const int t = bx - tg * noc;
-  const int ot = t % a.otiles, ct = t / a.otiles;
-  const int o0 = ot * 64, c0 = ct * BC;
+  const int tg = k.tg, o0 = k.o0, c0 = k.c0;
   const size_t HW = (size_t)H * W;
   const unsigned HWu = (unsigned)HW;
-  int ntiles = a.g.B * a.tiles_img;
-  if constexpr (MULTI) ntiles = P.use_tiles * P.nuse;
-  const int tbeg = by * a.chunks_per_split;
-  const int tend = min(ntiles, tbeg + a.chunks_per_split);
-  const bool do_bias = a.gbias && ct == 0 && tg == 0;
-  const float galpha = a.galpha;
+  const int tbeg = k.tbeg, tend = k.tend;
+  const bool do_bias = k.do_bias;
+  const float galpha = k.galpha;
   float gr[8], yr[GACT ? 8 : 1], xr[8 * NJ], bsum[8];
   unsigned gmask = 0, xmask = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) bsum[j] = 0.f;
   auto load = [&](int tile) {
-    const float* __restrict__ Gp = a.G;
-    const float* __restrict__ Yp = a.gy;
-    KSlice sbase = kernarg_srcs();
-    if constexpr (MULTI) {
-      const int u = tile / P.use_tiles;
-      tile -= u * P.use_tiles;
-      Gp = *(KFPtr)(kernarg_base() + offsetof(WgMulti, uG) + u * sizeof(FPtr));
-      if (GACT) Yp = *(KFPtr)(kernarg_base() + offsetof(WgMulti, uy) + u * sizeof(FPtr));
-      sbase = (KSlice)(kernarg_base() + offsetof(WgMulti, usrc)) + u * kMaxSrc;
+    const float* __restrict__ Gp = k.G;
+    const float* __restrict__ Yp = k.gy;
+    KSlice sbase = k.srcs;
+    if constexpr (TABLE) {
+      const int u = tile / k.use_tiles;
+      tile -= u * k.use_tiles;
+      Gp = *(KFPtr)(kernarg_base() + k.uG + u * sizeof(FPtr));
+      if (GACT) Yp = *(KFPtr)(kernarg_base() + k.uy + u * sizeof(FPtr));
+      sbase = (KSlice)(kernarg_base() + k.usrc) + u * kMaxSrc;
     }
-    const int b = tile / a.tiles_img, trem = tile - b * a.tiles_img;
-    const int ty0 = (trem / a.tiles_x) * TH, tx0 = (trem % a.tiles_x) * TW;
+    const int b = tile / k.tiles_img, trem = tile - b * k.tiles_img;
+    const int ty0 = (trem / k.tiles_x) * TH, tx0 = (trem % k.tiles_x) * TW;
     // G tile: lane = pixel of the tile, wave w -> output channels o0 + 8w + j
     const int qy = lane / TW, qx = lane - qy * TW;
     const int oy = ty0 + qy, ox = tx0 + qx;
@@ -1382,15 +1389,17 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(typename WgParam<MULTI>::T 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[tp][r] = 0.f;
 
+  // the block's tiles: tfirst + tl * tstep for tl in [tbeg, tend)
+  const int tfirst = k.tfirst, tstep = k.tstep;
   if (tbeg < tend) {
-    load(tbeg);
+    load(tfirst + tbeg * tstep);
     store(0);
   }
   __syncthreads();
   for (int tl = tbeg; tl < tend; ++tl) {
     const int buf = (tl - tbeg) & 1;
     const bool more = tl + 1 < tend;
-    if (more) load(tl + 1);
+    if (more) load(tfirst + (tl + 1) * tstep);
     const float* Gs = smem + buf * STAGE;
     const float* Xs = Gs + 64 * GPAD;
     const float* ga = Gs + hi * GPAD + wo * 32 + (lane & 31);
@@ -1431,7 +1440,7 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(typename WgParam<MULTI>::T 
   // partials [split][tap][o][c]: lanes run along c, so each store is a
   // 128-B row segment (the [o][c][tap] order of wgrad_halo_kernel scattered
   // them 36 B apart -- 7x write amplification measured at this split count)
-  float* wpart = a.part + (size_t)by * Cout * Cin * T;
+  float* wpart = k.wpart;
   const int c = c0 + wc * 32 + (lane & 31);
   const size_t tstride = (size_t)Cout * Cin;
   if (TAPSPLIT) {
@@ -1471,9 +1480,134 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(typename WgParam<MULTI>::T 
     for (int j = 0; j < 8; ++j) {
       const float v = wave_sum(bsum[j]);
       const int o = o0 + wave * 8 + j;
-      if (lane == 0 && o < Cout) a.bpart[(size_t)by * Cout + o] = v;
+      if (lane == 0 && o < Cout) k.bpart[o] = v;
     }
   }
+}
+
+template <int KH, int KW, int GACT, bool MULTI, int TG>
+__global__ __launch_bounds__(512) void wgrad2_kernel(typename WgParam<MULTI>::T P) {
+  const IgArgs& a = WgParam<MULTI>::ig(P);
+  constexpr int BC = HaloShapeW2<KH, KW, TG>::BC, T = KH * KW;
+  const int Cin = a.g.Cin, Cout = a.g.Cout;
+  const int noc = a.otiles * ((Cin + BC - 1) / BC);
+  // XCD-aware block order: the blocks of consecutive splits (adjacent pixel
+  // runs: their halo rows share cache lines) and the channel tiles of one split
+  // (they stage the same G / X tiles) land on the same XCD, i.e. the same L2
+  const int nbx = (int)gridDim.x;
+  const int lin = xcd_remap((int)(blockIdx.x + blockIdx.y * gridDim.x), (int)(gridDim.x * gridDim.y));
+  const int bx = lin % nbx, by = lin / nbx;
+  const int tg = TG == 1 ? 0 : bx / noc;    // kernel row of this block (TG == 3)
+  const int t = bx - tg * noc;
+  const int ot = t % a.otiles, ct = t / a.otiles;
+  int ntiles = a.g.B * a.tiles_img;
+  if constexpr (MULTI) ntiles = P.use_tiles * P.nuse;
+  WgBlock k;
+  k.H = a.g.H, k.W = a.g.W, k.Cin = Cin, k.Cout = Cout;
+  k.cb1 = a.cbase[1], k.cb2 = a.cbase[2], k.cb3 = a.cbase[3];
+  k.tiles_x = a.tiles_x, k.tiles_img = a.tiles_img, k.use_tiles = 0;
+  k.o0 = ot * 64, k.c0 = ct * BC, k.tg = tg;
+  k.tbeg = by * a.chunks_per_split;
+  k.tend = min(ntiles, k.tbeg + a.chunks_per_split);
+  k.tfirst = 0, k.tstep = 1;
+  k.do_bias = a.gbias && ct == 0 && tg == 0;
+  k.galpha = a.galpha;
+  k.wpart = a.part + (size_t)by * Cout * Cin * T;
+  k.bpart = a.bpart + (size_t)by * Cout;
+  k.G = a.G, k.gy = a.gy, k.srcs = kernarg_srcs();
+  k.uG = k.uy = k.usrc = 0;
+  if constexpr (MULTI) {
+    k.use_tiles = P.use_tiles;
+    k.uG = offsetof(WgMulti, uG), k.uy = offsetof(WgMulti, uy), k.usrc = offsetof(WgMulti, usrc);
+  }
+  wgrad2_block<KH, KW, GACT, MULTI, TG>(k);
+}
+
+// ------------------------------------------------------------------ grouped weight gradient
+// Several weights of one kernel shape and activation in ONE launch and one
+// finish: a launch costs a full-chip load burst, a wave of partial stores and
+// a graph node whatever the K extent behind it, and the step's weights are
+// each too small to amortise that alone.  The grid is one wave of blocks
+// shared over the members (wgrad_group_plan.hpp); a block finds its member in
+// a prefix table and reads that member's geometry, partial regions and use
+// slots from the kernel-argument segment with a block-uniform index.  The K
+// loop, LDS layout and partial layout are wgrad2_kernel's.
+struct WgGroupMember {
+  int H, W, Cin, Cout, cb1, cb2, cb3;
+  int tiles_x, tiles_img, use_tiles, ntiles;
+  int otiles, noc, splits;
+  int use0;               // first use slot
+  int block0, fin0, fin_blocks;   // first block in the main and the finish grid, finish blocks
+  int finish_q, wacc;
+  float galpha;
+  float* part;            // [splits][T][Cout][Cin]
+  float* bpart;           // [splits][Cout]
+  float* gweight;
+  float* gbias;           // nullable: no bias gradient for this member
+};
+
+struct WgGroupHead {      // all the finish needs
+  int T;
+  int block0[kGroupMembers];   // first block of each member (INT_MAX past the last)
+  int fin0[kGroupMembers];     // the same for the finish launch
+  WgGroupMember m[kGroupMembers];
+};
+
+struct WgGroup {
+  WgGroupHead h;
+  Slice usrc[kGroupUses][kMaxSrc];
+  const float* uG[kGroupUses];
+  const float* uy[kGroupUses];
+};
+static_assert(sizeof(WgGroup) <= 4096, "grouped weight gradient: kernel arguments over 4 KiB");
+
+typedef __attribute__((address_space(4))) const WgGroupMember* KMember;
+
+// member of block `id`: block0 / fin0 are read with constant indices
+__device__ __forceinline__ int group_member_of(const int (&first)[kGroupMembers], int id) {
+  int mi = 0;
+#pragma unroll
+  for (int i = 1; i < kGroupMembers; ++i) mi += id >= first[i] ? 1 : 0;
+  return mi;
+}
+
+template <int KH, int KW, int GACT>
+__global__ __launch_bounds__(512) void wgrad2_group_kernel(WgGroup P) {
+  constexpr int T = KH * KW;
+  // XCD order over the whole grid: a member's consecutive blocks (the channel
+  // tiles of one split, then the next split) stay on one XCD as in wgrad2_kernel
+  const int lin = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int mi = group_member_of(P.h.block0, lin);
+  const KMember km = (KMember)(kernarg_base() + offsetof(WgGroup, h) + offsetof(WgGroupHead, m)) + mi;
+  const int local = lin - km->block0;
+  const int noc = km->noc, otiles = km->otiles;
+  const int by = local / noc, t = local - by * noc;
+  const int ot = t % otiles, ct = t / otiles;
+  const int Cin = km->Cin, Cout = km->Cout, use0 = km->use0;
+  WgBlock k;
+  k.H = km->H, k.W = km->W, k.Cin = Cin, k.Cout = Cout;
+  k.cb1 = km->cb1, k.cb2 = km->cb2, k.cb3 = km->cb3;
+  k.tiles_x = km->tiles_x, k.tiles_img = km->tiles_img, k.use_tiles = km->use_tiles;
+  k.o0 = ot * 64, k.c0 = ct * 64, k.tg = 0;
+  // Split `by` takes every splits-th pixel tile, not a contiguous run: the
+  // blocks that run together on an XCD then stage ADJACENT tiles, whose halo
+  // rows and 128-B lines they share through that XCD's L2.  Measured on the
+  // fnet group (4 x 64->64 3x3, B=6, 48x160; FETCH_SIZE as counted): 193.5 MB
+  // with contiguous runs of 12 tiles, 52.2 MB this way (its four single
+  // launches, 3-tile runs whose XCD regions fit the L2: 4 x 12.3 MB).
+  const int splits = km->splits, ntiles = km->ntiles;
+  k.tbeg = 0;
+  k.tend = (ntiles - by + splits - 1) / splits;
+  k.tfirst = by, k.tstep = splits;
+  k.do_bias = km->gbias && ct == 0;
+  k.galpha = km->galpha;
+  k.wpart = km->part + (size_t)by * Cout * Cin * T;
+  k.bpart = km->bpart + (size_t)by * Cout;
+  k.G = nullptr, k.gy = nullptr, k.srcs = kernarg_srcs();
+  k.uG = (unsigned)(offsetof(WgGroup, uG) + use0 * sizeof(FPtr));
+  k.uy = (unsigned)(offsetof(WgGroup, uy) + use0 * sizeof(FPtr));
+  k.usrc = (unsigned)(offsetof(WgGroup, usrc) + use0 * kMaxSrc * sizeof(Slice));
+  wgrad2_block<KH, KW, GACT, true, 1>(k);
 }
 
 
@@ -1483,16 +1617,24 @@ __global__ __launch_bounds__(512) void wgrad2_kernel(typename WgParam<MULTI>::T 
 // of a wave share one element: lane group q sums the q-th contiguous range of
 // splits (split_sum, 4 chains), and the Q range sums are combined by shuffles
 // in a fixed tree -- the same order on every run.
+struct WgFinish {         // one weight's partials and targets; block `block` of `nblocks`
+  const float* part;
+  const float* bpart;
+  float* gweight;
+  float* gbias;
+  int wacc, Cout, Cin, T, splits, block, nblocks;
+};
+
 template <int Q>
-__global__ __launch_bounds__(256) void wgrad2_finish_kernel(IgArgs a, int splits) {
+__device__ __forceinline__ void wgrad2_finish_block(const WgFinish& a) {
   constexpr int EPW = 64 / Q;                     // elements per wave
-  const int Cout = a.g.Cout, Cin = a.g.Cin, T = a.g.KH * a.g.KW;
+  const int Cout = a.Cout, Cin = a.Cin, T = a.T, splits = a.splits;
   const long long oc = (long long)Cout * Cin, total = oc * T;
   const int lane = threadIdx.x & 63, q = lane / EPW, le = lane - q * EPW;
   const int per = (splits + Q - 1) / Q;
   const int s0 = min(splits, q * per), n = min(splits, s0 + per) - s0;
-  const long long wstride = (long long)gridDim.x * (blockDim.x / 64) * EPW;
-  for (long long eb = ((long long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6)) * EPW; eb < total;
+  const long long wstride = (long long)a.nblocks * (blockDim.x / 64) * EPW;
+  for (long long eb = ((long long)a.block * (blockDim.x / 64) + (threadIdx.x >> 6)) * EPW; eb < total;
        eb += wstride) {
     const long long e = eb + le;
     const bool ok = e < total;
@@ -1512,11 +1654,36 @@ __global__ __launch_bounds__(256) void wgrad2_finish_kernel(IgArgs a, int splits
     }
   }
   if (a.gbias) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < Cout; e += gridDim.x * blockDim.x) {
+    for (int e = a.block * blockDim.x + threadIdx.x; e < Cout; e += a.nblocks * blockDim.x) {
       const float bv = split_sum(a.bpart + e, (size_t)Cout, splits);
       a.gbias[e] = a.wacc ? a.gbias[e] + bv : bv;
     }
   }
+}
+
+template <int Q>
+__global__ __launch_bounds__(256) void wgrad2_finish_kernel(IgArgs a, int splits) {
+  WgFinish f;
+  f.part = a.part, f.bpart = a.bpart, f.gweight = a.gweight, f.gbias = a.gbias, f.wacc = a.wacc;
+  f.Cout = a.g.Cout, f.Cin = a.g.Cin, f.T = a.g.KH * a.g.KW, f.splits = splits;
+  f.block = (int)blockIdx.x, f.nblocks = (int)gridDim.x;
+  wgrad2_finish_block<Q>(f);
+}
+
+// Finish of a grouped launch: every member keeps its own split count, its own
+// Q (lanes per element, block-uniform) and its own accumulate flag.
+__global__ __launch_bounds__(256) void wgrad2_group_finish_kernel(WgGroupHead P) {
+  const int id = (int)blockIdx.x;
+  const int mi = group_member_of(P.fin0, id);
+  const KMember km = (KMember)(kernarg_base() + offsetof(WgGroupHead, m)) + mi;
+  WgFinish f;
+  f.part = km->part, f.bpart = km->bpart, f.gweight = km->gweight, f.gbias = km->gbias, f.wacc = km->wacc;
+  f.Cout = km->Cout, f.Cin = km->Cin, f.T = P.T, f.splits = km->splits;
+  f.block = id - km->fin0, f.nblocks = km->fin_blocks;
+  const int Q = km->finish_q;
+  if (Q == 4) wgrad2_finish_block<4>(f);
+  else if (Q == 2) wgrad2_finish_block<2>(f);
+  else wgrad2_finish_block<1>(f);
 }
 
 static void launch_wgrad2_finish(const IgArgs& a, int splits, hipStream_t s) {
@@ -3745,6 +3912,145 @@ extern "C" int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse,
   else
     hipLaunchKernelGGL(wgrad_halo_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, wh.splits);
   return launch_status("wgrad_halo_finish_kernel launch failed");
+}
+
+// ------------------------------------------------------------------ grouped weight gradient (host)
+namespace dro {
+namespace {
+
+// Checks a group's members and plans the launch; with `g`, also fills the
+// kernel arguments except the workspace pointers.  Nothing is launched.
+int group_setup(const dro_wgrad_member* members, int nmember, int KH, int KW, int act, WgGroupPlan* pl,
+                WgGroup* g) {
+  if (!members) {
+    set_error("conv2d_weight_grad_group: NULL members");
+    return DRO_E_NULL;
+  }
+  if (nmember < 1 || nmember > kGroupMembers) {
+    set_error("conv2d_weight_grad_group: need 1..8 members per call (dro_conv2d_weight_grad_group_capacity)");
+    return DRO_E_SHAPE;
+  }
+  if (!wgrad_group_shape_ok(KH, KW)) {
+    set_error("conv2d_weight_grad_group: kernel shape not supported (1x1, 1x5, 5x1, 3x3)");
+    return DRO_E_SHAPE;
+  }
+  if (act < 0 || act > 3) {
+    set_error("conv2d_weight_grad_group: unknown activation");
+    return DRO_E_MODE;
+  }
+  WgGroupShape shapes[kGroupMembers];
+  int nuse = 0, st;
+  for (int i = 0; i < nmember; ++i) {
+    const dro_wgrad_member& mb = members[i];
+    if (!mb.uses || !mb.grad_weight) {
+      set_error("conv2d_weight_grad_group: NULL uses/grad_weight");
+      return DRO_E_NULL;
+    }
+    if (mb.nuse < 1 || mb.nuse > kGroupUsesPerMember) {
+      set_error("conv2d_weight_grad_group: need 1..16 uses per member");
+      return DRO_E_SHAPE;
+    }
+    if (nuse + mb.nuse > kGroupUses) {
+      set_error("conv2d_weight_grad_group: more uses than use slots (dro_conv2d_weight_grad_group_capacity)");
+      return DRO_E_SHAPE;
+    }
+    IgArgs first = {};
+    for (int u = 0; u < mb.nuse; ++u) {
+      IgArgs t = {};
+      if ((st = conv_setup_geom(t, mb.uses[u].srcs, mb.nsrc, mb.B, mb.H, mb.W, mb.Cout, KH, KW))) return st;
+      if (!mb.uses[u].dout || (act != 0 && !mb.uses[u].y)) {
+        set_error("conv2d_weight_grad_group: NULL dout (or y with an activation)");
+        return DRO_E_NULL;
+      }
+      if (u == 0) first = t;
+      for (int j = 0; j < kMaxSrc; ++j)
+        if (t.cbase[j] != first.cbase[j]) {
+          set_error("conv2d_weight_grad_group: uses split the input channels differently");
+          return DRO_E_SHAPE;
+        }
+      if (g) {
+        for (int j = 0; j < kMaxSrc; ++j) g->usrc[nuse + u][j] = t.src[j];
+        g->uG[nuse + u] = mb.uses[u].dout;
+        g->uy[nuse + u] = act ? mb.uses[u].y : nullptr;
+      }
+    }
+    shapes[i] = {mb.nuse, mb.B, mb.H, mb.W, first.g.Cin, mb.Cout};
+    if (g) {
+      WgGroupMember& m = g->h.m[i];
+      m.H = mb.H, m.W = mb.W, m.Cin = first.g.Cin, m.Cout = mb.Cout;
+      m.cb1 = first.cbase[1], m.cb2 = first.cbase[2], m.cb3 = first.cbase[3];
+      m.galpha = mb.alpha;
+      m.gweight = mb.grad_weight;
+      m.gbias = mb.grad_bias;
+      m.wacc = mb.accumulate ? 1 : 0;
+    }
+    nuse += mb.nuse;
+  }
+  static const int target = [] {   // tuning override: DRO_WGG_TARGET_BLOCKS (default 256)
+    const int v = env_int("DRO_WGG_TARGET_BLOCKS", 0);
+    return v > 0 ? v : kGroupTarget;
+  }();
+  if (!wgrad_group_plan(shapes, nmember, KH, KW, target, pl)) {
+    set_error("conv2d_weight_grad_group: the group cannot be planned");
+    return DRO_E_SHAPE;
+  }
+  return DRO_OK;
+}
+
+}  // namespace
+}  // namespace dro
+
+extern "C" int dro_conv2d_weight_grad_group_capacity(int* max_members, int* max_uses) {
+  if (max_members) *max_members = kGroupMembers;
+  if (max_uses) *max_uses = kGroupUses;
+  return (int)sizeof(WgGroup);
+}
+
+extern "C" size_t dro_conv2d_weight_grad_group_workspace_bytes(const dro_wgrad_member* members, int nmember,
+                                                              int KH, int KW) {
+  WgGroupPlan pl;
+  return group_setup(members, nmember, KH, KW, 0, &pl, nullptr) == DRO_OK ? pl.bytes : 0;
+}
+
+extern "C" int dro_conv2d_weight_grad_group(const dro_wgrad_member* members, int nmember, int KH, int KW,
+                                            int act, void* workspace, size_t workspace_bytes, void* stream) {
+  WgGroup g = {};
+  WgGroupPlan pl;
+  int st;
+  if ((st = group_setup(members, nmember, KH, KW, act, &pl, &g))) return st;
+  if ((st = check_ws(workspace, workspace_bytes, pl.bytes, "conv2d_weight_grad_group"))) return st;
+  char* ws = static_cast<char*>(workspace);
+  const int T = KH * KW;
+  double flops = 0.0;
+  g.h.T = T;
+  for (int i = 0; i < kGroupMembers; ++i) g.h.block0[i] = g.h.fin0[i] = INT_MAX;
+  for (int i = 0; i < nmember; ++i) {
+    const WgGroupMemberPlan& p = pl.m[i];
+    WgGroupMember& m = g.h.m[i];
+    m.tiles_x = p.tiles_x, m.tiles_img = p.tiles_img, m.use_tiles = p.use_tiles, m.ntiles = p.ntiles;
+    m.otiles = p.otiles, m.noc = p.otiles * p.ctiles;
+    m.splits = p.splits;
+    m.use0 = p.use0;
+    m.block0 = g.h.block0[i] = p.block0;
+    m.fin0 = g.h.fin0[i] = p.fin0;
+    m.fin_blocks = p.fin_blocks;
+    m.finish_q = p.finish_q;
+    m.part = reinterpret_cast<float*>(ws + p.part_off);
+    m.bpart = reinterpret_cast<float*>(ws + p.bpart_off);
+    flops += 2.0 * m.Cout * m.Cin * T * (double)members[i].B * m.H * m.W * members[i].nuse;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)pl.blocks);
+  conv_logf(flops, "wgrad2_group_kernel<%d, %d, %d>", KH, KW, act);
+#define DRO_WGG(KH_, KW_) DRO_ACT_SWITCH(act, hipLaunchKernelGGL((wgrad2_group_kernel<KH_, KW_, A_>), grid, dim3(512), 0, s, g))
+  if (KH == 1 && KW == 1) { DRO_WGG(1, 1); }
+  else if (KH == 1) { DRO_WGG(1, 5); }
+  else if (KW == 1) { DRO_WGG(5, 1); }
+  else { DRO_WGG(3, 3); }
+#undef DRO_WGG
+  if ((st = launch_status("wgrad2_group_kernel launch failed"))) return st;
+  hipLaunchKernelGGL(wgrad2_group_finish_kernel, dim3((unsigned)pl.fin_blocks), dim3(256), 0, s, g.h);
+  return launch_status("wgrad2_group_finish_kernel launch failed");
 }
 
 // ------------------------------------------------------------------ SepConvGRU elementwise backward

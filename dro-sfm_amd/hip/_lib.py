@@ -99,6 +99,9 @@ def load():
     _sig(lib.dro_conv2d_backward, P, I, P, I, I, I, I, I, I, I, F, P, P, P, P, P, P, P, P, I, P, P, Z, S)
     _sig(lib.dro_conv2d_weight_grad_multi_workspace_bytes, I, I, I, I, I, I, I, I, restype=Z)
     _sig(lib.dro_conv2d_weight_grad_multi, P, I, I, I, I, I, I, I, I, I, F, P, P, I, P, Z, S)
+    _sig(lib.dro_conv2d_weight_grad_group_capacity, P, P)
+    _sig(lib.dro_conv2d_weight_grad_group_workspace_bytes, P, I, I, I, restype=Z)
+    _sig(lib.dro_conv2d_weight_grad_group, P, I, I, I, I, P, Z, S)
     _sig(lib.dro_adam_step, P, P, P, P, ctypes.c_longlong, P, P, S)
     _sig(lib.dro_gru_backward_elem, I, I, I, I, I, P, P, P, P, P, P, P, P, S)
     _sig(lib.dro_convgru_candidate_backward, P, I, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, Z, S)
@@ -137,6 +140,8 @@ EXPORTED = (
     "dro_conv2d_workspace_bytes", "dro_conv2d_plan", "dro_debug_conv_stamps", "dro_conv_log", "dro_conv_log_read", "dro_conv2d_forward", "dro_convgru_gates_forward",
     "dro_convgru_blend_forward", "dro_conv2d_backward",
     "dro_conv2d_weight_grad_multi_workspace_bytes", "dro_conv2d_weight_grad_multi",
+    "dro_conv2d_weight_grad_group_capacity", "dro_conv2d_weight_grad_group_workspace_bytes",
+    "dro_conv2d_weight_grad_group",
     "dro_gru_backward_elem", "dro_convgru_candidate_backward", "dro_convgru_gates_backward", "dro_adam_step",
     "dro_bn_state_bytes", "dro_bn_apply", "dro_bn_backward_apply", "dro_conv2d_bn_forward", "dro_conv2d_bn_backward_data",
 )

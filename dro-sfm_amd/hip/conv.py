@@ -34,6 +34,20 @@ it once the last use has been back-propagated, so the bucket's all-reduce
 overlaps the rest of the backward), or at the end of backward (engine final
 callback) for whatever is still queued.  set_batched_weight_grads.
 
+Grouped weight gradients (default on, set_grouped_weight_grads /
+DRO_GROUPED_WGRAD=0): a complete weight is not launched from its hook but
+joins the group of the stream it was queued from, keyed by (KH, KW, act);
+a group -- up to 8 weights / 24 uses, the capacity of the kernel-argument
+tables -- is ONE dro_conv2d_weight_grad_group launch + one finish, issued on
+that stream when it is full, when the gradient bucket that holds one of its
+targets completes while gradients are being reduced (flush_ready_groups), or
+at the end of backward.  The encoders' single-use weights, never pending
+together before, now share launches: 66 + 66 weight-gradient launches per
+bench step became 17 + 18, 14.82 -> 14.17 ms per step.
+Their queued output gradients stay alive until the flush (about 100 MB at
+the KITTI metric shape).  Weights queued from several streams, with more
+than 16 uses, or of the 7x7 shapes keep the per-weight launch.
+
 Split-bf16 engine (set_split_engine, default off): the 1x5 / 5x1 / 3x3 / 1x1
 forward and data-gradient GEMMs run on bf16 MFMA over operands split into three
 bf16 terms (csrc/xconv.hip, f32 accuracy at 2.67x the f32 MFMA rate).  Each
@@ -298,13 +312,70 @@ def _covers(t, ptr_):
     return t is not None and t.data_ptr() <= ptr_ < t.data_ptr() + t.numel() * t.element_size()
 
 
+class DroWgradMember(ctypes.Structure):
+    _fields_ = [("uses", ctypes.c_void_p), ("nuse", ctypes.c_int), ("nsrc", ctypes.c_int),
+                ("B", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cout", ctypes.c_int),
+                ("alpha", ctypes.c_float), ("grad_weight", ctypes.c_void_p), ("grad_bias", ctypes.c_void_p),
+                ("accumulate", ctypes.c_int)]
+
+
+# Grouped weight gradients (default on; DRO_GROUPED_WGRAD=0 for A/B runs):
+# complete items -- every use queued -- wait in _READY, keyed by (stream they
+# were queued from, KH, KW, act), until their group is launched.
+_GROUPED = [os.environ.get("DRO_GROUPED_WGRAD", "1") != "0"]
+_READY = {}
+_GROUP_CAP = []
+GROUP_LAUNCHES = []    # (KH, KW, act, members) of every grouped launch while GROUP_LOG[0] (tests, profiles)
+GROUP_LOG = [False]
+
+
+def set_grouped_weight_grads(enabled):
+    """Launch the queued weight gradients in groups -- several weights of one
+    kernel shape and activation, queued from one stream, per launch (True,
+    default) -- or one launch per weight as soon as it is complete (False)."""
+    _GROUPED[0] = bool(enabled)
+
+
+def _group_capacity():
+    if not _GROUP_CAP:
+        m, u = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.load().dro_conv2d_weight_grad_group_capacity(ctypes.byref(m), ctypes.byref(u))
+        _GROUP_CAP[:] = [m.value, u.value]
+    return _GROUP_CAP
+
+
+def _groupable(item):
+    meta, uses, streams = item
+    return (_GROUPED[0] and (meta[5], meta[6]) in _MULTI_SHAPES and len(streams) == 1
+            and len(uses) <= _MAX_USES)
+
+
+def _ready(item):
+    """A complete item joins its stream's group; a group that cannot take it
+    (capacity, or a member that writes the same gradient) is launched first."""
+    meta, uses, streams = item
+    key = (streams[0], meta[5], meta[6], meta[7])
+    group = _READY.setdefault(key, [])
+    max_members, max_uses = _group_capacity()
+    if (len(group) + 1 > max_members or sum(len(it[1]) for it in group) + len(uses) > max_uses
+            or any(it[0][9].data_ptr() == meta[9].data_ptr() for it in group)):
+        _launch_group(key, _READY.pop(key))
+        group = _READY.setdefault(key, [])
+    group.append(item)
+    if len(group) == max_members or sum(len(it[1]) for it in group) == max_uses:
+        _launch_group(key, _READY.pop(key))
+    return streams[0]
+
+
 def flush_param_grads(param):
-    """Launch now the queued weight gradients that write into `param.grad`
+    """The queued weight gradients that write into `param.grad` are complete
     (trainers/dp_trainer.GradBuckets calls this from the parameter's
     post-accumulate hook: autograd runs that hook once every use of the
-    parameter has been back-propagated, so the queue holds all of its uses and
-    its bucket's all-reduce can start while the rest of the backward runs).
-    Returns the stream the launches were queued on, or None."""
+    parameter has been back-propagated).  Grouped: they join the group of the
+    stream they were queued from, which is launched when it is full, when a
+    gradient bucket that holds one of its targets completes
+    (flush_ready_groups) or at the end of backward.  Not grouped: launched
+    now.  Returns the stream the launches go to, or None."""
     g = param.grad
     if g is None or not _PENDING:
         return None
@@ -313,18 +384,78 @@ def flush_param_grads(param):
     if not keys:
         return None
     items = [_PENDING.pop(k) for k in keys]
-    return _launch_weight_grads(items, items[0][2][0])
+    stream = items[0][2][0]
+    single = [it for it in items if not _groupable(it)]
+    for it in items:
+        if _groupable(it):
+            _ready(it)
+    if single:
+        _launch_weight_grads(single, stream)
+    return stream
+
+
+def flush_ready_groups(lo=None, hi=None):
+    """Launch the waiting groups -- all of them, or those with a weight-gradient
+    target inside the address range [lo, hi) (a gradient bucket that is about
+    to be reduced).  Returns the streams launched on."""
+    streams = set()
+    for key in list(_READY):
+        group = _READY[key]
+        if lo is None or any(lo <= t.data_ptr() < hi for it in group for t in it[0][9:11] if t is not None):
+            _launch_group(key, _READY.pop(key))
+            streams.add(key[0])
+    return streams
 
 
 def flush_weight_grads(stream=None):
-    """Launch every queued weight gradient (one launch + one reduction per
-    weight per 16 uses), in first-use order; releases the kept tensors."""
+    """Launch every queued weight gradient, in first-use order, and release
+    the kept tensors: grouped per queueing stream (the current stream then
+    waits for the other streams' groups), or one launch + one reduction per
+    weight per 16 uses on `stream`."""
     _PENDING_CB[0] = False
-    if not _PENDING:
-        return
     items = list(_PENDING.values())
     _PENDING.clear()
-    _launch_weight_grads(items, stream or torch.cuda.current_stream())
+    single = [it for it in items if not _groupable(it)]
+    for it in items:
+        if _groupable(it):
+            _ready(it)
+    cur = torch.cuda.current_stream()
+    for s in flush_ready_groups():
+        if s != cur:
+            cur.wait_stream(s)
+    if single:
+        _launch_weight_grads(single, stream or cur)
+
+
+def _launch_group(key, group):
+    """One grouped launch + one finish for the items of `group` on their stream."""
+    if not group:
+        return
+    lib = _lib.load()
+    stream, KH, KW, act = key
+    n = len(group)
+    keep, members = [], (DroWgradMember * n)()
+    for i, (meta, uses, _) in enumerate(group):
+        B, H, W, Cin, Cout, _, _, _, alpha, gw, gb, nsrc, _ = meta
+        sl = [_slices(srcs) for srcs, _, _ in uses]
+        arr = (DroWgradUse * len(uses))()
+        for j, (_, dout, y) in enumerate(uses):
+            arr[j].srcs = ctypes.cast(sl[j], ctypes.c_void_p)
+            arr[j].dout = dout.data_ptr()
+            arr[j].y = y.data_ptr() if y is not None else None
+        keep.append((sl, arr))
+        m = members[i]
+        m.uses, m.nuse, m.nsrc = ctypes.cast(arr, ctypes.c_void_p), len(uses), nsrc
+        m.B, m.H, m.W, m.Cout, m.alpha = B, H, W, Cout, alpha
+        m.grad_weight, m.grad_bias, m.accumulate = gw.data_ptr(), gb.data_ptr() if gb is not None else None, 1
+    if GROUP_LOG[0]:
+        GROUP_LAUNCHES.append((KH, KW, act, [(len(u), *m[:5]) for m, u, _ in group]))
+    with torch.cuda.stream(stream):
+        nb = int(lib.dro_conv2d_weight_grad_group_workspace_bytes(members, n, KH, KW))
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=group[0][0][9].device)
+        check(lib.dro_conv2d_weight_grad_group(members, n, KH, KW, act, ptr(ws), nb,
+                                               ctypes.c_void_p(stream.cuda_stream)),
+              "dro_conv2d_weight_grad_group")
 
 
 def _launch_weight_grads(items, stream):

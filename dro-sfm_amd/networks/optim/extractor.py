@@ -27,7 +27,9 @@ is the stem's 3x3/s2 max pooling (hip.maxpool3x3s2, bit-identical to
 F.max_pool2d forward and backward; ATen's backward took 55 us per call).
 The stride-1 3x3 convolutions (layer1-3, the fusion head with its concat read
 in place, out_conv) run on the HIP conv engine's halo-tiled kernels
-(conv3x3).  The 7x7/s2 stems, 3x3/s2 stage entries and 1x1/s2 downsamples
+(conv3x3); on the trainer path their weight gradients -- one use each -- are
+launched in groups of up to 8 weights per stream (hip/conv.py, grouped weight
+gradients).  The 7x7/s2 stems, 3x3/s2 stage entries and 1x1/s2 downsamples
 run on the flattened implicit GEMM with the stride (forward), its
 parity-class form (data gradient: each input-pixel parity class takes only
 its own taps) and the generic weight-gradient kernel -- no MIOpen in the

@@ -108,9 +108,13 @@ class GradBuckets:
     Autograd runs every parameter's post-accumulate hook once per backward,
     after the last use of that parameter has been back-propagated (for a
     direct one the hook sees the None the conv returned).  For a direct
-    parameter the hook first launches its queued weight-gradient kernel
-    (`direct_flush`, hip.conv.flush_param_grads on the GPU) and records the
-    stream it went to; then it counts down like any other.  A bucket is
+    parameter the hook first hands its queued weight gradient to the conv
+    engine (`direct_flush`, hip.conv.flush_param_grads on the GPU), which
+    launches it now or holds it for a grouped launch, and records the stream
+    it goes to; then it counts down like any other.  While gradients are
+    reduced, a bucket that completes first launches the held groups that
+    write into it (`bucket_flush`), so its collective never precedes them;
+    without a reduction they go out when full or at the end of backward.  A bucket is
     complete when all its parameters' hooks have run: the current stream waits
     for every stream that wrote into it, the adopted gradients are gathered,
     and an event marks the gathered state -- the all-reduce, issued later
@@ -137,8 +141,12 @@ class GradBuckets:
             self.offsets[p] = off
             p.grad = self.flat[off:off + p.numel()].view_as(p)
             off += p.numel()
+        # bucket_flush(lo, hi): launch the weight-gradient groups that wait with a
+        # target inside that address range (hip.conv.flush_ready_groups)
+        self.bucket_flush = None
         if direct_flush is None and self.flat.is_cuda:
-            from ..hip.conv import flush_param_grads as direct_flush
+            from ..hip.conv import flush_param_grads as direct_flush, flush_ready_groups
+            self.bucket_flush = flush_ready_groups
         self.direct_flush = direct_flush
         self.bucket_bytes = int(bucket_mb * 1024 * 1024)
         self.active = None            # params that receive gradients (learned on step 1)
@@ -227,6 +235,12 @@ class GradBuckets:
                 (self._bstreams[b] if wrote == cur else self._bside[b]).add(wrote)
         self._left[b] -= 1
         if self._left[b] == 0:
+            if self.reduce and self.bucket_flush is not None:
+                # grouped weight gradients are deferred past their hooks: the ones
+                # this bucket carries go out now, before its collective (their
+                # streams were recorded when their hooks ran)
+                sl = self._slice(self.buckets[b])
+                self.bucket_flush(sl.data_ptr(), sl.data_ptr() + sl.numel() * sl.element_size())
             self._complete(b)
             self._issue_ready()
 

@@ -532,6 +532,35 @@ int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse, int nsrc, 
                                  float* grad_bias, int accumulate, void* workspace,
                                  size_t workspace_bytes, void* stream);
 
+/* Grouped weight gradient: the weights of several convolutions that share
+ * (KH, KW, act) -- 1x1, 1x5, 5x1 or 3x3 -- in ONE launch plus one split
+ * reduction.  Each member is a weight with its own uses (1..16, as above),
+ * image size, channel counts and virtual-concat split, output scale and
+ * targets; the member and use tables travel in the kernel arguments (nothing
+ * is read from host memory after the call returns).  A group holds at most
+ * `max_members` members and `max_uses` uses over all members
+ * (the _capacity call, which returns the size in bytes of the kernel-argument
+ * struct); the caller cuts larger groups.  Results are bitwise run-to-run
+ * deterministic (fixed-order split sums, no atomics). */
+typedef struct dro_wgrad_member {
+  const dro_wgrad_use* uses; /* nuse uses of this weight */
+  int nuse;                  /* 1..16 */
+  int nsrc;                  /* input slices per use (the same channel split in every use) */
+  int B, H, W, Cout;
+  float alpha;               /* output scale of the forward (act none) */
+  float* grad_weight;        /* [Cout][Cin][KH][KW] */
+  float* grad_bias;          /* [Cout] or NULL */
+  int accumulate;            /* 1: add into grad_weight / grad_bias */
+} dro_wgrad_member;
+
+int dro_conv2d_weight_grad_group_capacity(int* max_members, int* max_uses);
+
+size_t dro_conv2d_weight_grad_group_workspace_bytes(const dro_wgrad_member* members, int nmember,
+                                                    int KH, int KW);
+
+int dro_conv2d_weight_grad_group(const dro_wgrad_member* members, int nmember, int KH, int KW,
+                                 int act, void* workspace, size_t workspace_bytes, void* stream);
+
 /* SepConvGRU backward, elementwise parts (update.py:67-70): with zr the saved
  * sigmoid gates [B,2hd,H,W] (z first), q the saved candidate [B,hd,H,W].
  * Outputs are gradients w.r.t. the gates' PRE-activations (feed them to
