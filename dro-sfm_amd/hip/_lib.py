@@ -77,6 +77,7 @@ def load():
     _sig(lib.dro_conv2d_strided_backward, P, P, P, I, I, I, I, I, I, I, I, I, P, I, P, P, I, P, Z, S)
     _sig(lib.dro_depth_metrics_demon_prepare, P, P, P, LL, I, I, I, I, I, F, F, P, P, P, S)
     _sig(lib.dro_depth_metrics_demon_reduce, P, P, P, P, LL, I, I, I, F, F, P, P, S)
+    _sig(lib.dro_post_process_inv_depth, P, P, I, I, I, I, P, P, P, S)
     _sig(lib.dro_resize_rgb8_to_tensor, P, I, I, I, I, I, P, P, I, P, P, I, P, P, S)
     _sig(lib.dro_color_jitter_rgb8, P, I, I, I, P, P, S)
     _sig(lib.dro_resize_rgb8, P, I, I, I, I, I, P, P, I, P, P, I, P, P, S)
@@ -130,7 +131,7 @@ EXPORTED = (
     "dro_maxpool3x3s2_forward", "dro_maxpool3x3s2_backward",
     "dro_depth_metrics_blocks", "dro_depth_metrics_workspace_bytes", "dro_depth_metrics_prepare",
     "dro_depth_metrics_reduce", "dro_depth_metrics_median_workspace_bytes", "dro_depth_metrics_median",
-    "dro_depth_metrics_demon_prepare", "dro_depth_metrics_demon_reduce",
+    "dro_depth_metrics_demon_prepare", "dro_depth_metrics_demon_reduce", "dro_post_process_inv_depth",
     "dro_conv2d_strided_workspace_bytes", "dro_conv2d_strided_forward", "dro_conv2d_strided_backward",
     "dro_pose_mean_forward", "dro_pose_mean_backward",
     "dro_resize_rgb8_to_tensor", "dro_color_jitter_rgb8", "dro_resize_rgb8", "dro_rgb8_to_tensor",

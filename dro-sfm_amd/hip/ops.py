@@ -1229,3 +1229,29 @@ def depth_metrics_demon(gt, gt_pose, pred, min_depth, max_depth, use_gt_scale=Tr
     return out
 
 
+_POST_METHODS = {"mean": 0, "max": 1, "min": 2}
+
+
+def post_process_inv_depth(inv_depth, inv_depth_flipped, method="mean"):
+    """post_process_inv_depth (dro_sfm/utils/depth.py:202-256) plus the two
+    inv2depth calls of ModelWrapper.evaluate_depth (model_wrapper.py:361-371)
+    on the GPU, one launch.
+
+    inv_depth [B,1,H,W] the prediction, inv_depth_flipped [B,1,H,W] the
+    prediction on the left-right flipped inputs (not flipped back).  Returns
+    (inv_pp, depth, depth_pp), float32 [B,1,H,W] each: the border-blended fused
+    inverse depth, inv2depth(inv_depth) and inv2depth(inv_pp)."""
+    lib = _lib.load()
+    require_device(inv_depth, inv_depth_flipped, what="post_process_inv_depth")
+    if method not in _POST_METHODS:
+        raise ValueError("Unknown post-process method {}".format(method))
+    if inv_depth.dim() != 4 or inv_depth.shape[1] != 1 or inv_depth_flipped.shape != inv_depth.shape:
+        raise RuntimeError("post_process_inv_depth: inv_depth and inv_depth_flipped [B,1,H,W] of one shape expected")
+    B, _, H, W = inv_depth.shape
+    inv, flipped = inv_depth.contiguous(), inv_depth_flipped.contiguous()
+    inv_pp = torch.empty(B, 1, H, W, device=inv.device, dtype=torch.float32)
+    depth, depth_pp = torch.empty_like(inv_pp), torch.empty_like(inv_pp)
+    check(lib.dro_post_process_inv_depth(ptr(inv), ptr(flipped), B, H, W, _POST_METHODS[method], ptr(inv_pp),
+                                         ptr(depth), ptr(depth_pp), stream_of(inv)),
+          "dro_post_process_inv_depth")
+    return inv_pp, depth, depth_pp

@@ -38,9 +38,12 @@ backward -> (all-reduce) -> Adam step.
 import os
 import sys
 import time
+from collections import OrderedDict
 
 import torch
 import torch.distributed as dist
+
+from ..models.evaluate import evaluate_depth
 
 
 def graph_safe_nccl_env():
@@ -671,6 +674,51 @@ class DataParallelTrainer:
     def step(self, batch, **fwd_kw):
         self.model.train()
         return self._step_inner(batch, **fwd_kw)
+
+    def validate(self, loader, params, demon=False, evaluate=evaluate_depth):
+        """One validation epoch (HorovodTrainer.validate -> validation_step ->
+        ModelWrapper.evaluate_depth, horovod_trainer.py:129-155 and
+        model_wrapper.py:355-399): `evaluate(model, batch, params, demon=demon)`
+        on every batch of `loader`, averaged over samples (each batch weighted
+        by its size) and over the ranks of the trainer's group.  Returns an
+        OrderedDict metrics name + mode -> float32 tensor [12] on the model's
+        device (empty when no batch carried ground truth).
+
+        The sums stay on the device (no host synchronisation in the loop) and
+        the ranks exchange them once, packed with the sample count.  Eager, on
+        the current stream, in eval mode: parameters, BatchNorm buffers,
+        gradients and optimizer state are only read, so it can run between two
+        GraphedTrainStep.step calls.  Every rank must see the same metric
+        names (checked)."""
+        modes = [(m, m.training) for m in self.model.modules()]
+        self.model.eval()
+        dev = self.grads.flat.device
+        names, sums, count = (), None, torch.zeros(1, device=dev)
+        try:
+            for batch in loader:
+                metrics = evaluate(self.model, batch, params, demon=demon)["metrics"]
+                if not metrics:
+                    continue
+                vals = torch.stack([v.float() for v in metrics.values()])
+                if sums is None:
+                    names, sums = tuple(metrics), torch.zeros_like(vals)
+                elif tuple(metrics) != names:
+                    raise RuntimeError(f"validate: metric names changed between batches ({tuple(metrics)} vs {names})")
+                B = batch["rgb"].shape[0]
+                sums += vals * B
+                count += B
+        finally:
+            for m, training in modes:
+                m.training = training
+        group = self.grads.group
+        check_same_across_ranks(names, group, dev, "validation metric names")
+        if sums is None:
+            return OrderedDict()
+        if dist.is_initialized() and dist.get_world_size(group) > 1:
+            packed = torch.cat([sums.flatten(), count])
+            dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
+            sums, count = packed[:-1].view_as(sums), packed[-1:]
+        return OrderedDict(zip(names, (sums / count).unbind(0)))
 
 
 def _clone_batch(batch):

@@ -28,6 +28,29 @@ def disp_to_depth(disp, min_depth, max_depth):
     return scaled, 1.0 / scaled
 
 
+def fuse_inv_depth(inv_depth, inv_depth_hat, method='mean'):
+    """fuse_inv_depth (dro_sfm/utils/depth.py:202-227 of the reference), same
+    signature: the mean / max / min of an inverse depth map and the flipped-back
+    map of the flipped pass."""
+    if method == 'mean':
+        return 0.5 * (inv_depth + inv_depth_hat)
+    elif method == 'max':
+        return torch.max(inv_depth, inv_depth_hat)
+    elif method == 'min':
+        return torch.min(inv_depth, inv_depth_hat)
+    raise ValueError('Unknown post-process method {}'.format(method))
+
+
+def post_process_inv_depth(inv_depth, inv_depth_flipped, method='mean'):
+    """post_process_inv_depth (dro_sfm/utils/depth.py:230-256 of the reference),
+    same signature and return value: the post-processed inverse depth map
+    [B,1,H,W].  One HIP launch (csrc/evalpost.hip); GPU tensors only."""
+    if method not in ('mean', 'max', 'min'):
+        raise ValueError('Unknown post-process method {}'.format(method))
+    from .. import hip
+    return hip.post_process_inv_depth(inv_depth, inv_depth_flipped, method=method)[0]
+
+
 def compute_depth_metrics(config, gt, pred, use_gt_scale=True):
     """compute_depth_metrics (dro_sfm/utils/depth.py:259-343 of the reference),
     same signature and return value: a tensor [9] of abs_rel, sq_rel, rmse,
@@ -70,17 +93,19 @@ def compute_pose_metrics(config, gt, pred):
     """compute_pose_metrics (dro_sfm/utils/depth.py:400-421 of the reference):
     [rotation error (deg), translation direction error (deg), scale-fitted
     translation error (cm)] of the first reference's pose (gt[0], pred[0] a
-    Pose or a [1,4,4] tensor).  The reference takes the pair to the host and
+    Pose or a [B,4,4] tensor).  The reference takes the pair to the host and
     computes in numpy float32; here the same formulas run in float64 on the
-    pair's device (no host synchronisation), returned as float32."""
+    pair's device (no host synchronisation), returned as float32.  The
+    reference's formula holds for one sample (its validation loaders use
+    batch size 1); a larger batch gives the mean of the per-sample errors."""
     pm = pred[0].mat if hasattr(pred[0], "mat") else pred[0]
-    pr = pm.detach().squeeze().double()
-    g = gt[0].detach().squeeze().to(pr.device).double()
-    R1, t1, R2, t2 = g[:3, :3], g[:3, 3], pr[:3, :3], pr[:3, 3]
-    cos_r = torch.clamp_max(((R1 * R2).sum() - 1.0) / 2.0, 1.0)          # trace(R1^T R2)
+    pr = pm.detach().double().reshape(-1, 4, 4)
+    g = gt[0].detach().to(pr.device).double().reshape(-1, 4, 4)
+    R1, t1, R2, t2 = g[:, :3, :3], g[:, :3, 3], pr[:, :3, :3], pr[:, :3, 3]
+    cos_r = torch.clamp_max(((R1 * R2).sum((1, 2)) - 1.0) / 2.0, 1.0)    # trace(R1^T R2)
     rdeg = torch.arccos(cos_r) * (180.0 / math.pi)
-    cos_t = (t1 * t2).sum() / (t1.norm() * t2.norm())
+    cos_t = (t1 * t2).sum(1) / (t1.norm(dim=1) * t2.norm(dim=1))
     tdeg = torch.arccos(cos_t) * (180.0 / math.pi)
-    a = (t1 * t2).sum() / (t2 * t2).sum()
-    tcm = 100.0 * torch.sqrt(((t1 - a * t2) ** 2).sum())
-    return torch.stack([rdeg, tdeg, tcm]).float()
+    a = (t1 * t2).sum(1) / (t2 * t2).sum(1)
+    tcm = 100.0 * torch.sqrt(((t1 - a.unsqueeze(1) * t2) ** 2).sum(1))
+    return torch.stack([rdeg, tdeg, tcm], 1).mean(0).float()

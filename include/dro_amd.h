@@ -50,7 +50,7 @@ extern "C" {
 #define DRO_E_MODE (-3)     /* unknown pose/depth mode or option     */
 
 const char* dro_last_error(void);
-int dro_abi_version(void);   /* 10: BatchNorm fused into the 3x3 convs (dro_conv2d_bn_forward / dro_conv2d_bn_backward_data, dro_bn_state_bytes); 9: dro_png_decode (GPU PNG inflate + unfilter); 8: dro_convgru_candidate_backward / dro_convgru_gates_backward (the GRU's elementwise stages in the conv data-gradient epilogues); 7: warp-cost forward/backward take ref_layout (channels-last reference maps); 6: photometric calls take clip_loss (and the backward the l1_signs test hook); 5: warp-cost / photometric backward take the `cells` test hook, view synthesis entry points; 4: convex upsample takes the fused add/mul; 3: conv calls take split-bf16 weights (dro_weight_split); 2: dro_adam_step reads its hyper-parameters from device memory */
+int dro_abi_version(void);   /* 10 (additive since, version unchanged: dro_post_process_inv_depth, the evaluation step's flip post-processing); 10: BatchNorm fused into the 3x3 convs (dro_conv2d_bn_forward / dro_conv2d_bn_backward_data, dro_bn_state_bytes); 9: dro_png_decode (GPU PNG inflate + unfilter); 8: dro_convgru_candidate_backward / dro_convgru_gates_backward (the GRU's elementwise stages in the conv data-gradient epilogues); 7: warp-cost forward/backward take ref_layout (channels-last reference maps); 6: photometric calls take clip_loss (and the backward the l1_signs test hook); 5: warp-cost / photometric backward take the `cells` test hook, view synthesis entry points; 4: convex upsample takes the fused add/mul; 3: conv calls take split-bf16 weights (dro_weight_split); 2: dro_adam_step reads its hyper-parameters from device memory */
 
 /* In-graph step timeline (diagnostics, tools/step_timeline.py): record the
  * device's constant-rate real-time counter into buf[slot] when `stream`
@@ -299,6 +299,19 @@ int dro_depth_metrics_demon_reduce(const float* gt, const float* pred_up, const 
                                    const float* gt_pose, long long pose_stride, int B, int H, int W,
                                    float min_depth, float max_depth, float* metrics, void* workspace,
                                    void* stream);
+
+/* Test-time flip post-processing of the evaluation step: post_process_inv_depth
+ * (dro_sfm/utils/depth.py:202-256 of the reference) and the two inv2depth calls
+ * of ModelWrapper.evaluate_depth (dro_sfm/models/model_wrapper.py:361-371) in
+ * one launch.  inv [B,1,H,W] the prediction, inv_flipped [B,1,H,W] the
+ * prediction on the left-right flipped inputs (still flipped).  With
+ * bh = inv_flipped[b,y,W-1-x], f = fuse(inv, bh) (method 0 mean, 1 max, 2 min),
+ * mask = 1 - clamp(20 (linspace(0,1,W)[x] - 0.05), 0, 1) and mask_hat its
+ * mirror: inv_pp = mask_hat inv + mask bh + (1 - mask - mask_hat) f,
+ * depth = inv2depth(inv), depth_pp = inv2depth(inv_pp) (each [B,1,H,W]).
+ * B 1..65535, W >= 2. */
+int dro_post_process_inv_depth(const float* inv, const float* inv_flipped, int B, int H, int W,
+                               int method, float* inv_pp, float* depth, float* depth_pp, void* stream);
 
 /* Resize + ToTensor of decoded uint8 RGB frames, bit-identical to Pillow's
  * BILINEAR resampling (torchvision Resize on PIL images, datasets/
