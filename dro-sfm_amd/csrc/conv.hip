@@ -520,7 +520,9 @@ __global__ __launch_bounds__(256 * KS) void dconv_kernel(IgArgs a) {
   const float galpha = a.galpha;
   // weights are staged as float4 runs (a run never crosses a weight row: RUN %
   // 4 == 0); starts need only dword alignment; per-thread offsets are chunk
-  // independent.  Tensors of < 4 weights take the flat path (plan_igemm).
+  // independent.  A run past the end of the tensor is clamped to its last
+  // four weights, which is only right when no run straddles the end: tensors
+  // whose row length Cin * T is no multiple of 4 take the flat path (plan_igemm).
   constexpr int W4 = S::WTOT / 4, WPER4 = (W4 + 255) / 256;
   constexpr int WREG = 4 * WPER4;
   static_assert(S::WTOT % 4 == 0 && RUN % 4 == 0, "float4 weight runs");
@@ -1964,7 +1966,7 @@ __global__ __launch_bounds__(256) void fwd_k7s2_kernel(IgArgs a) {
   constexpr int KSTEPS = (NK + 1) / 2, NPE = CIN * PD * PD, PPER = (NPE + 255) / 256;
   __shared__ float Ws[64 * KP];
   __shared__ float Ps[CIN * PD * PDP + 1];
-  __shared__ int koff[2 * KSTEPS];      // patch offset of column k (the zero slot past NK)
+  __shared__ int koff[2 * KSTEPS];      // patch offset of column k (-1: the padded column past NK)
   const int Cout = a.g.Cout, B = a.g.B, Ho = a.g.H, Wo = a.g.W, Hi = a.Hs, Wi = a.Ws;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int oh = wave & 1, ph = wave >> 1, h = lane >> 5;
@@ -1980,11 +1982,20 @@ __global__ __launch_bounds__(256) void fwd_k7s2_kernel(IgArgs a) {
   if (tid < 64) Ws[tid * KP + NK] = 0.f;
   for (int k = tid; k < 2 * KSTEPS; k += 256) {
     const int tap = k / CIN, c = k - tap * CIN, ty = tap / 7, tx = tap - ty * 7;
-    koff[k] = k < NK ? (c * PD + ty) * PDP + tx : CIN * PD * PDP;
+    koff[k] = k < NK ? (c * PD + ty) * PDP + tx : -1;
   }
-  if (tid == 0) Ps[CIN * PD * PDP] = 0.f;
+  constexpr int ZERO = CIN * PD * PDP;  // the zero slot, Ps's last element
+  if (tid == 0) Ps[ZERO] = 0.f;
   const int pl = ph * 32 + (lane & 31), py = pl >> 3, px = pl & 7;
   const int poff = S * py * PDP + S * px;
+  // Ps index range: a real column reads koff + poff <= ((CIN - 1) PD + 6) PDP + 6
+  // + 14 PDP + 14 = (CIN PD - 1) PDP + 20 = ZERO - 1 (PD = PDP = 21); the padded
+  // column (NK odd: CIN == 3) reads ZERO itself, never ZERO + poff (as
+  // wgrad_k7_kernel's boff < 0).  No lane's index exceeds ZERO.
+  auto bidx = [&](int k) {
+    const int ko = koff[k];
+    return ko < 0 ? ZERO : ko + poff;
+  };
   float pr[PPER];
   auto load_tile = [&](int t) {
     const int b = t / tis, r0 = t - b * tis, tyi = r0 / txs, txi = r0 - tyi * txs;
@@ -2021,13 +2032,13 @@ __global__ __launch_bounds__(256) void fwd_k7s2_kernel(IgArgs a) {
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    float an = wrow[0], bn = Ps[koff[h] + poff];
+    float an = wrow[0], bn = Ps[bidx(h)];
 #pragma unroll 8
     for (int s2 = 0; s2 < KSTEPS; ++s2) {
       const float av = an, bv = bn;
       if (s2 + 1 < KSTEPS) {
         an = wrow[2 * (s2 + 1)];
-        bn = Ps[koff[2 * (s2 + 1) + h] + poff];
+        bn = Ps[bidx(2 * (s2 + 1) + h)];
       }
       acc = mfma32(av, bv, acc);
     }
@@ -2100,11 +2111,20 @@ void halo_fill(IgPlan& pl) {
   pl.lds_bytes = S::LDS * sizeof(float);
 }
 
-IgPlan plan_igemm(int rows, int kch, int KH, int KW, int B, int H, int W) {
+// cin: the weight tensor's input channels (kch in the forward, rows in the data
+// gradient), 0 when unknown (no row-length rule)
+IgPlan plan_igemm(int rows, int kch, int KH, int KW, int B, int H, int W, int cin) {
   const bool shape_ok = (KH == 1 && KW == 5) || (KH == 5 && KW == 1) || (KH == 3 && KW == 3) ||
                         (KH == 1 && KW == 1);
-  // the halo kernel stages weights as float4 runs: tensors of < 4 weights go flat
-  if (!shape_ok || (long long)rows * kch * KH * KW < 4) return plan_igemm_flat(rows, kch, KH, KW, B, H, W);
+  // the halo kernel stages weights as float4 runs that start at multiples of 4
+  // within a weight row [Cin][T] and clamps a run that would pass the end of
+  // the tensor to its last four weights: with a row length Cin * T that is no
+  // multiple of 4 the last row's final run straddles the end and would be
+  // staged shifted (wrong taps for the last channel), so those tensors -- and
+  // the ones of < 4 weights -- go flat
+  const bool ragged_rows = cin > 0 && ((long long)cin * KH * KW) % 4 != 0;
+  if (!shape_ok || (long long)rows * kch * KH * KW < 4 || ragged_rows)
+    return plan_igemm_flat(rows, kch, KH, KW, B, H, W);
   IgPlan pl = {};
   const long long P = (long long)B * H * W;
   pl.halo = true;
@@ -2301,7 +2321,7 @@ WhPlan plan_wgrad2(int Cin, int Cout, int KH, int KW, int ntiles_total, int B, i
 }
 
 size_t fwd_workspace(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
-  return std::max(plan_igemm(Cout, Cin, KH, KW, B, H, W).part_bytes,
+  return std::max(plan_igemm(Cout, Cin, KH, KW, B, H, W, Cin).part_bytes,
                   xconv_part_bytes(Cout, Cin, KH, KW, B, H, W));
 }
 
@@ -2309,7 +2329,7 @@ size_t bwd_workspace(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
   const long long P = (long long)B * H * W;
   const int T = KH * KW;
   return align256((size_t)Cout * P * sizeof(float)) +              // pre-activation gradient
-         std::max(plan_igemm(Cin, Cout, KH, KW, B, H, W).part_bytes,  // data-gradient split-K
+         std::max(plan_igemm(Cin, Cout, KH, KW, B, H, W, Cin).part_bytes,  // data-gradient split-K
                   xconv_part_bytes(Cin, Cout, KH, KW, B, H, W)) +
          std::max(std::max(plan_wgrad(Cin, Cout, T, P).part_bytes,  // weight-gradient partials
                            plan_wgrad_halo(Cin, Cout, KH, KW, B, H, W).part_bytes),
@@ -2701,7 +2721,7 @@ unsigned long long* g_conv_stamps = nullptr;   // dro_debug_conv_stamps
 template <int MODE, int ACT, int EPI, int XF = 0>
 int launch_igemm(IgArgs& a, long long P, char* ws, hipStream_t s) {
   IgPlan pl = a.flat_only ? plan_igemm_flat(a.rows, a.kch, a.g.KH, a.g.KW, a.g.B, a.g.H, a.g.W)
-                          : plan_igemm(a.rows, a.kch, a.g.KH, a.g.KW, a.g.B, a.g.H, a.g.W);
+                          : plan_igemm(a.rows, a.kch, a.g.KH, a.g.KW, a.g.B, a.g.H, a.g.W, a.g.Cin);
   // BN fused into the conv (BnFuse): 3x3 halo kernel only, and no split-K for
   // the statistics epilogues (the blocks' own tiles are the partials)
   constexpr bool BNF = EPI >= 5 || XF != 0;
@@ -2836,17 +2856,22 @@ int check_ws(const void* ws, size_t have, size_t need, const char* what) {
     default: set_error("conv2d: unknown activation"); return DRO_E_MODE; \
   }
 
-extern "C" int dro_conv2d_plan(int rows, int kch, int KH, int KW, int B, int H, int W, long long* info) {
-  if (!info || rows < 1 || kch < 1 || KH < 1 || KW < 1 || B < 1 || H < 1 || W < 1) {
+extern "C" int dro_conv2d_plan_cin(int rows, int kch, int KH, int KW, int B, int H, int W, int cin,
+                                   long long* info) {
+  if (!info || rows < 1 || kch < 1 || KH < 1 || KW < 1 || B < 1 || H < 1 || W < 1 || cin < 0) {
     set_error("conv2d_plan: bad arguments");
     return DRO_E_SHAPE;
   }
-  const IgPlan pl = plan_igemm(rows, kch, KH, KW, B, H, W);
+  const IgPlan pl = plan_igemm(rows, kch, KH, KW, B, H, W, cin);
   const long long v[16] = {pl.halo, pl.bm, pl.row_tiles, pl.ptiles, pl.ksplit, pl.chunks_per_split,
                            pl.TH, pl.TW, pl.HWd, pl.HPAD, pl.tiles_x, pl.tiles_img, pl.CK,
                            (long long)pl.lds_bytes, (long long)pl.part_bytes, pl.kin};
   for (int i = 0; i < 16; ++i) info[i] = v[i];
   return DRO_OK;
+}
+
+extern "C" int dro_conv2d_plan(int rows, int kch, int KH, int KW, int B, int H, int W, long long* info) {
+  return dro_conv2d_plan_cin(rows, kch, KH, KW, B, H, W, 0, info);
 }
 
 extern "C" int dro_conv_log(int enable) {
@@ -3168,7 +3193,7 @@ extern "C" int dro_conv2d_bn_backward_data(const float* weight, int B, int H, in
   IgArgs a = {};
   int st = conv_setup_geom(a, &sl, 1, B, H, W, Cout, 3, 3);
   if (st) return st;
-  if ((st = check_ws(workspace, workspace_bytes, plan_igemm(Cin, Cout, 3, 3, B, H, W).part_bytes,
+  if ((st = check_ws(workspace, workspace_bytes, plan_igemm(Cin, Cout, 3, 3, B, H, W, Cin).part_bytes,
                      "conv2d_bn_backward_data")))
     return st;
   a.weight = weight;
@@ -3370,12 +3395,12 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
   char* ws = static_cast<char*>(workspace);
   char* ws_pre = ws;
   char* ws_ig = ws_pre + align256((size_t)Cout * P * sizeof(float));
-  char* ws_wg = ws_ig + std::max(plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W).part_bytes,
+  char* ws_wg = ws_ig + std::max(plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W, a.g.Cin).part_bytes,
                                  xconv_part_bytes(a.g.Cin, Cout, KH, KW, B, H, W));
   // fold the activation derivative into the halo kernels' G staging when both
   // gradients run there (dense y); otherwise form G first
   const WhPlan wh = plan_wgrad_halo(a.g.Cin, Cout, KH, KW, B, H, W);
-  const bool halo_dgrad = plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W).halo;
+  const bool halo_dgrad = plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W, a.g.Cin).halo;
   // the thin data gradient (7x7 over <= 8 input channels, one source) folds
   // as well; a call without a weight gradient (the trainer queues those)
   // needs only its data-gradient kernel to fold
@@ -3645,6 +3670,33 @@ extern "C" size_t dro_conv2d_strided_workspace_bytes(int B, int Hi, int Wi, int 
   size_t wg = plan_wgrad(Cin, Cout, KH * KW, (long long)B * Ho * Wo).part_bytes;
   if (k7_ok(KH, KW, Cin, pad, stride)) wg = std::max(wg, k7_part_bytes(B, Ho, Wo, Cin, Cout));
   return std::max(fwd, align256(dg) + wg);
+}
+
+extern "C" int dro_conv2d_strided_plan(int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride,
+                                       int pad, long long* info) {
+  if (!info || B < 1 || Hi < 1 || Wi < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || pad < 0 ||
+      (stride != 1 && stride != 2)) {
+    set_error("conv2d_strided_plan: bad arguments");
+    return DRO_E_SHAPE;
+  }
+  const int Ho = (Hi + 2 * pad - KH) / stride + 1, Wo = (Wi + 2 * pad - KW) / stride + 1;
+  if (Ho < 1 || Wo < 1) {
+    set_error("conv2d_strided_plan: empty output");
+    return DRO_E_SHAPE;
+  }
+  const IgPlan f = plan_igemm_flat(Cout, Cin, KH, KW, B, Ho, Wo);
+  long long d[3];
+  if (stride == 2) {
+    const ClassPlan cp = plan_class_dgrad(B, Hi, Wi, Cin, Cout, KH, KW);
+    d[0] = cp.bm, d[1] = cp.ksplit, d[2] = 1;
+  } else {
+    const IgPlan g = plan_igemm_flat(Cin, Cout, KH, KW, B, Hi, Wi);
+    d[0] = g.bm, d[1] = g.ksplit, d[2] = 0;
+  }
+  const long long v[8] = {f.bm, f.ksplit, d[0], d[1], d[2], k7_ok(KH, KW, Cin, pad, stride) ? 1 : 0,
+                          k7_splits(B, Ho, Wo), plan_wgrad(Cin, Cout, KH * KW, (long long)B * Ho * Wo).splits};
+  for (int i = 0; i < 8; ++i) info[i] = v[i];
+  return DRO_OK;
 }
 
 extern "C" int dro_conv2d_strided_forward(const float* x, const float* weight, const float* bias, int B, int Hi,

@@ -89,6 +89,8 @@ def load():
     _sig(lib.dro_batchnorm_relu_backward, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, Z, S)
     _sig(lib.dro_conv2d_workspace_bytes, I, I, I, I, I, I, I, restype=Z)
     _sig(lib.dro_conv2d_plan, I, I, I, I, I, I, I, P)
+    _sig(lib.dro_conv2d_plan_cin, I, I, I, I, I, I, I, I, P)
+    _sig(lib.dro_conv2d_strided_plan, I, I, I, I, I, I, I, I, I, P)
     _sig(lib.dro_debug_conv_stamps, P)
     _sig(lib.dro_conv_log, I)
     _sig(lib.dro_conv_log_read, ctypes.c_char_p, ctypes.c_longlong, restype=ctypes.c_longlong)
@@ -138,7 +140,7 @@ EXPORTED = (
     "dro_png_filtered_bytes", "dro_png_decode",
     "dro_batchnorm_workspace_bytes", "dro_batchnorm_relu_forward", "dro_batchnorm_relu_backward",
     "dro_weight_split_bytes", "dro_weight_split",
-    "dro_conv2d_workspace_bytes", "dro_conv2d_plan", "dro_debug_conv_stamps", "dro_conv_log", "dro_conv_log_read", "dro_conv2d_forward", "dro_convgru_gates_forward",
+    "dro_conv2d_workspace_bytes", "dro_conv2d_plan", "dro_conv2d_plan_cin", "dro_conv2d_strided_plan", "dro_debug_conv_stamps", "dro_conv_log", "dro_conv_log_read", "dro_conv2d_forward", "dro_convgru_gates_forward",
     "dro_convgru_blend_forward", "dro_conv2d_backward",
     "dro_conv2d_weight_grad_multi_workspace_bytes", "dro_conv2d_weight_grad_multi",
     "dro_conv2d_weight_grad_group_capacity", "dro_conv2d_weight_grad_group_workspace_bytes",

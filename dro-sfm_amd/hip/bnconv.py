@@ -116,7 +116,12 @@ def site_of(bn, shape, device):
 def supported(bn, conv, x, elems=None):
     """The fused path applies: a training-mode BN with momentum after a 3x3
     stride-1 'same' conv without bias on a float32 CUDA tensor, with `elems`
-    (the BN's elements per channel, B*H*W) above the size policy's bound."""
+    (the BN's elements per channel, B*H*W) above the size policy's bound.
+    The fused epilogues exist in the halo kernel only, which takes weight
+    tensors whose rows [Cin][3][3] are a multiple of 4 long (csrc/conv.hip
+    plan_igemm)."""
+    if conv.weight.shape[1] % 4 != 0:
+        return False
     if _MODE[0] == "0" or (_MODE[0] == "large" and (elems if elems is not None else
                                                     x.shape[0] * x.shape[2] * x.shape[3]) <= _LARGE):
         return False

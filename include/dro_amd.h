@@ -434,8 +434,20 @@ size_t dro_conv2d_workspace_bytes(int B, int H, int W, int Cin, int Cout, int KH
  * gradient (rows = Cin, kch = Cout) would use, as 16 integers: halo, BM,
  * row tiles, pixel tiles, K splits, chunks per split, TH, TW, halo row width,
  * channel stride, tiles per row, tiles per image, channels per chunk, LDS bytes,
- * split-K partial bytes, 0. */
+ * split-K partial bytes, wave groups per tile (kin). */
 int dro_conv2d_plan(int rows, int kch, int KH, int KW, int B, int H, int W, long long* info);
+/* The same with the weight tensor's input channels given (cin = kch for the
+ * forward, rows for the data gradient): weight rows [cin][KH][KW] whose length
+ * is no multiple of 4 take the flat kernel.  cin = 0: as dro_conv2d_plan. */
+int dro_conv2d_plan_cin(int rows, int kch, int KH, int KW, int B, int H, int W, int cin, long long* info);
+
+/* Diagnostics: the launch plans of dro_conv2d_strided_* for this shape, as 8
+ * integers: forward BM, forward K splits, data-gradient BM, data-gradient K
+ * splits, 1 when the data gradient runs per parity class (stride 2), 1 when
+ * the weight gradient runs on the 7x7 kernel, its block count, the generic
+ * weight gradient's pixel splits. */
+int dro_conv2d_strided_plan(int B, int Hi, int Wi, int Cin, int Cout, int KH, int KW, int stride, int pad,
+                            long long* info);
 
 /* Diagnostics only: with a device buffer of >= 16 * (grid blocks) u64, every
  * following halo-conv launch writes per-block s_memtime stamps (kernel start,
