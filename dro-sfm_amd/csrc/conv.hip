@@ -1010,243 +1010,15 @@ __device__ __forceinline__ __attribute__((address_space(4))) const char* kernarg
 }
 
 // ------------------------------------------------------------------ halo-tiled weight gradient
-// dW[o, c, tap] = sum_p G[o, p] X[c, p + d(tap)] for (KH, KW) in {1x5, 5x1, 3x3}:
-// block = 64 output channels x 32 input channels x all taps, K = the pixels of
-// a run of TH x TW pixel tiles.  Per tile the G tile [64 px][64 o] and the X
-// patch [32 c][halo] are staged once; tap (ty, tx) reads the patch shifted.
-// Waves: 2 (o halves) x 2, the second pair splitting either the taps (3x3:
-// 5 + 4 per wave, no reduction) or the pixels (T = 5: summed through LDS at
-// the end, one tap at a time).  Blocks of channel tile 0 also sum G over their
-// pixels for the bias.  Partials: weights [split][Cout][Cin][T], bias [split][Cout].
-template <int KH, int KW>
-struct HaloShapeW {
-  static constexpr int T = KH * KW;
-  // 3x3: taps split 5 + 4 over the wave pairs (all 9 taps per wave over half
-  // the pixels measured no faster and needs 512 registers per lane)
-  static constexpr bool TAPSPLIT = T == 9;
-  static constexpr int TPW = TAPSPLIT ? 5 : T;   // accumulators (taps) per wave
-  static constexpr int TH = HaloShape<32, KH, KW>::TH, TW = 64 / TH;
-  static constexpr int HWd = TW + KW - 1;
-  static constexpr int HALO = (TH + KH - 1) * HWd;
-  static constexpr int HPAD = HALO | 1;          // odd: lanes read 32 channels at stride HPAD
-  static constexpr int NJ = (HALO + 63) / 64;
-  static constexpr int BC = 32;                  // input channels per block
-  static constexpr int GPAD = 65;                // [px][o] row stride
-  static constexpr int STAGE = 64 * GPAD + BC * HPAD;
-  static constexpr int LDS = 2 * STAGE > 2 * 16 * 64 * 2 ? 2 * STAGE : 2 * 16 * 64 * 2;
-  static_assert(NJ <= 2 && TW % 2 == 0, "halo shape");
-};
-
-template <int KH, int KW, int GACT, bool MULTI>
-__global__ __launch_bounds__(256) void wgrad_halo_kernel(typename WgParam<MULTI>::T P) {
-  const IgArgs& a = WgParam<MULTI>::ig(P);
-  using S = HaloShapeW<KH, KW>;
-  constexpr int T = S::T, TH = S::TH, TW = S::TW, HWd = S::HWd, HALO = S::HALO, HPAD = S::HPAD;
-  constexpr int NJ = S::NJ, BC = S::BC, GPAD = S::GPAD, STAGE = S::STAGE, TPW = S::TPW;
-  constexpr bool TAPSPLIT = S::TAPSPLIT;
-  constexpr int PH = KH / 2, PW = KW / 2;
-  __shared__ float smem[S::LDS];
-  const int cb1 = a.cbase[1], cb2 = a.cbase[2], cb3 = a.cbase[3];
-  const int H = a.g.H, W = a.g.W, Cin = a.g.Cin, Cout = a.g.Cout;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = blockIdx.x;
-  const int ot = t % a.otiles, ct = t / a.otiles;
-  const int o0 = ot * 64, c0 = ct * BC;
-  const size_t HW = (size_t)H * W;
-  const unsigned HWu = (unsigned)HW;
-  int ntiles = a.g.B * a.tiles_img;
-  if constexpr (MULTI) ntiles = P.use_tiles * P.nuse;
-  const int tbeg = blockIdx.y * a.chunks_per_split;
-  const int tend = min(ntiles, tbeg + a.chunks_per_split);
-  const bool do_bias = a.gbias && ct == 0;
-  const float galpha = a.galpha;
-  float gr[16], yr[GACT ? 16 : 1], xr[8 * NJ], bsum[16];
-  unsigned gmask = 0, xmask = 0;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) bsum[j] = 0.f;
-  auto load = [&](int tile) {
-    const float* __restrict__ Gp = a.G;
-    const float* __restrict__ Yp = a.gy;
-    KSlice sbase = kernarg_srcs();
-    if constexpr (MULTI) {   // wave-uniform use index: its sources, G and y from the kernarg table
-      const int u = tile / P.use_tiles;
-      tile -= u * P.use_tiles;
-      Gp = *(KFPtr)(kernarg_base() + offsetof(WgMulti, uG) + u * sizeof(FPtr));
-      if (GACT) Yp = *(KFPtr)(kernarg_base() + offsetof(WgMulti, uy) + u * sizeof(FPtr));
-      sbase = (KSlice)(kernarg_base() + offsetof(WgMulti, usrc)) + u * kMaxSrc;
-    }
-    const int b = tile / a.tiles_img, trem = tile - b * a.tiles_img;
-    const int ty0 = (trem / a.tiles_x) * TH, tx0 = (trem % a.tiles_x) * TW;
-    // G tile: lane = pixel of the tile, wave w -> output channels o0 + 16w + j
-    const int qy = lane / TW, qx = lane - qy * TW;
-    const int oy = ty0 + qy, ox = tx0 + qx;
-    const bool pin = oy < H && ox < W;
-    const unsigned pix = pin ? (unsigned)(oy * W + ox) : 0u;
-    gmask = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int o = o0 + wave * 16 + j;        // scalar
-      const bool ok = pin && o < Cout;
-      gmask |= ok ? (1u << j) : 0u;
-      const unsigned off = ok ? ((unsigned)b * Cout + o) * HWu + pix : 0u;
-      gr[j] = Gp[off];
-      if (GACT) yr[j] = Yp[off];
-    }
-    // X patch: wave w -> channels c0 + w + 4i, lanes over the halo
-    // every channel's descriptor first (independent scalar loads, one wait),
-    // then the patch loads
-    RowDesc ds[8];
-    bool real[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int ch = c0 + wave + 4 * i;          // scalar
-      real[i] = ch < Cin;
-      ds[i] = row_desc_at(sbase, cb1, cb2, cb3, real[i] ? ch : 0, HWu);
-    }
-    xmask = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const unsigned xbase = (unsigned)b * ds[i].A + ds[i].Bc;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int e = lane + 64 * j;
-        const int hy = e / HWd, hx = e - hy * HWd;
-        const int yy = ty0 - PH + hy, xx = tx0 - PW + hx;
-        const bool ok = real[i] && e < HALO && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-        xmask |= ok ? (1u << (i * NJ + j)) : 0u;
-        xr[i * NJ + j] = ds[i].p[ok ? xbase + (ds[i].M ? (unsigned)(yy * W + xx) : 0u) : 0u];
-      }
-    }
-  };
-  auto store = [&](int buf) {
-    float* Gs = smem + buf * STAGE;
-    float* Xs = Gs + 64 * GPAD;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      float g = (gmask >> j) & 1u ? galpha * gr[j] : 0.f;
-      if (GACT) g *= act_bwd(yr[j], GACT);
-      Gs[lane * GPAD + wave * 16 + j] = g;
-      if (do_bias) bsum[j] += g;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int e = lane + 64 * j;
-        if (e < HPAD) Xs[(wave + 4 * i) * HPAD + e] = (xmask >> (i * NJ + j)) & 1u ? xr[i * NJ + j] : 0.f;
-      }
-    }
-  };
-
-  const int wo = wave & 1, w2 = wave >> 1;       // o half; tap group (3x3) or pixel half
-  const int hi = lane >> 5;
-  const int tap0 = TAPSPLIT ? w2 * 5 : 0;         // first tap of this wave
-  const int ntap = TAPSPLIT ? (w2 == 0 ? 5 : 4) : T;
-  f32x16 acc[TPW];
-#pragma unroll
-  for (int tp = 0; tp < TPW; ++tp)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[tp][r] = 0.f;
-
-  unsigned long long* const stp = a.stamps ? a.stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 : nullptr;
-  auto stamp = [&](int k) {   // diagnostics (dro_debug_conv_stamps): 0 set-up, 12 first tile
-                                // staged, 1 prologue, 2.. tile iterations (<= 8), 13 loop done, 14 end
-    if (stp && threadIdx.x == 0 && k < 15) stp[k] = __builtin_amdgcn_s_memtime();
-  };
-  const int dbg = ablation_flags(a.dbg);      // 1 skip the loop's loads, 2 its MFMAs, 4 its LDS stores (invalid results)
-  stamp(0);
-  if (tbeg < tend) {
-    load(tbeg);
-    store(0);
-  }
-  stamp(12);
-  __syncthreads();
-  stamp(1);
-  for (int tl = tbeg; tl < tend; ++tl) {
-    const int buf = (tl - tbeg) & 1;
-    const bool more = tl + 1 < tend;
-    if (more && !(dbg & 1)) load(tl + 1);
-    const float* Gs = smem + buf * STAGE;
-    const float* Xs = Gs + 64 * GPAD;
-    const float* ga = Gs + hi * GPAD + wo * 32 + (lane & 31);
-    const float* xb = Xs + (lane & 31) * HPAD + hi;
-    constexpr int KS = TAPSPLIT ? 32 : 16;        // k-steps (pixel pairs) per wave
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      if (dbg & 2) break;
-      const int pp = 2 * ((TAPSPLIT ? 0 : w2 * 16) + s);   // even pixel of this k-step
-      const float av = ga[pp * GPAD];
-      const int poff = (pp / TW) * HWd + (pp % TW);
-#pragma unroll
-      for (int k = 0; k < TPW; ++k) {
-        if (k < ntap) {
-          const int tap = tap0 + k;
-          const int ty = tap / KW, tx = tap - ty * KW;
-          acc[k] = mfma32(av, xb[poff + ty * HWd + tx], acc[k]);
-        }
-      }
-    }
-    if (more && !(dbg & 4)) store(buf ^ 1);
-    __syncthreads();
-    if (tl - tbeg < 8) stamp(2 + tl - tbeg);
-  }
-  stamp(13);
-  float* wpart = a.part + (size_t)blockIdx.y * Cout * Cin * T;
-  const int c = c0 + (lane & 31);
-  if (TAPSPLIT) {
-#pragma unroll
-    for (int k = 0; k < TPW; ++k) {
-      if (k < ntap) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int o = o0 + wo * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          if (o < Cout && c < Cin) wpart[((size_t)o * Cin + c) * T + tap0 + k] = acc[k][r];
-        }
-      }
-    }
-  } else {   // sum the pixel halves one tap at a time
-    float* red = smem;   // [2 o halves][16][64]
-#pragma unroll
-    for (int tp = 0; tp < T; ++tp) {
-      if (w2 == 1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[(wo * 16 + r) * 64 + lane] = acc[tp][r];
-      }
-      __syncthreads();
-      if (w2 == 0) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int o = o0 + wo * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          if (o < Cout && c < Cin)
-            wpart[((size_t)o * Cin + c) * T + tp] = acc[tp][r] + red[(wo * 16 + r) * 64 + lane];
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (do_bias) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const float v = wave_sum(bsum[j]);
-      const int o = o0 + wave * 16 + j;
-      if (lane == 0 && o < Cout) a.bpart[(size_t)blockIdx.y * Cout + o] = v;
-    }
-  }
-  stamp(14);
-}
-
-// ------------------------------------------------------------------ weight gradient v2
-// dW[o, c, tap] = sum_p G[o, p] X[c, p + d(tap)]: block = 64 output x 64 input
-// channels x all taps, 8 waves (2 per SIMD), K = the pixels of a run of TH x TW
-// tiles.  Against wgrad_halo_kernel (64 x 32 channels, 4 waves): G is staged
-// once per 64 input channels instead of per 32 (half the G / y re-reads) and
-// two waves per SIMD hide the LDS -> MFMA latency the single wave left
-// exposed (profiles/r3_conv_roofline.json: 25 % of the f32 MFMA peak, 195 MB
-// fetched per 4.5 GFLOP launch).  Wave w: o half w & 1, c half (w >> 1) & 1,
-// group w >> 2 = tap group (3x3: taps 0-4 / 5-8) or pixel half (T <= 5:
-// summed through LDS at the end).  Same partials as wgrad_halo_kernel
-// ([split][Cout][Cin][T], bias [split][Cout]) and the same finish kernel.
+// dW[o, c, tap] = sum_p G[o, p] X[c, p + d(tap)] for (KH, KW) in {1x1, 1x5,
+// 5x1, 3x3}: block = 64 output x 64 input channels x all taps, 8 waves (2 per
+// SIMD), K = the pixels of a run of TH x TW pixel tiles.  Per tile the G tile
+// [64 px][64 o] and the X patch [64 c][halo] are staged once; tap (ty, tx)
+// reads the patch shifted.  Two waves per SIMD hide each other's LDS -> MFMA
+// latency.  Wave w: o half w & 1, c half (w >> 1) & 1, group w >> 2 = tap
+// group (3x3: taps 0-4 / 5-8) or pixel half (T <= 5: summed through LDS at
+// the end).  Blocks of channel tile 0 also sum G over their pixels for the
+// bias.  Partials: weights [split][T][Cout][Cin], bias [split][Cout].
 template <int KH, int KW, int TG>
 struct HaloShapeW2 {
   static constexpr int T = KH * KW;
@@ -1440,7 +1212,7 @@ __device__ __forceinline__ void wgrad2_block(const WgBlock& k) {
     __syncthreads();
   }
   // partials [split][tap][o][c]: lanes run along c, so each store is a
-  // 128-B row segment (the [o][c][tap] order of wgrad_halo_kernel scattered
+  // 128-B row segment (an [o][c][tap] order scattered
   // them 36 B apart -- 7x write amplification measured at this split count)
   float* wpart = k.wpart;
   const int c = c0 + wc * 32 + (lane & 31);
@@ -1696,23 +1468,6 @@ static void launch_wgrad2_finish(const IgArgs& a, int splits, hipStream_t s) {
   if (Q == 4) hipLaunchKernelGGL(wgrad2_finish_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, a, splits);
   else if (Q == 2) hipLaunchKernelGGL(wgrad2_finish_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, a, splits);
   else hipLaunchKernelGGL(wgrad2_finish_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, a, splits);
-}
-
-// dW[o][c][tap] = sum_s part[s][o][c][tap]; db[o] = sum_s bpart[s][o]
-__global__ __launch_bounds__(256) void wgrad_halo_finish_kernel(IgArgs a, int splits) {
-  const int Cout = a.g.Cout;
-  const long long total = (long long)Cout * a.g.Cin * a.g.KH * a.g.KW;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-    float v = 0.f;
-    v = split_sum(a.part + e, (size_t)total, splits);
-    a.gweight[e] = a.wacc ? a.gweight[e] + v : v;
-    if (a.gbias && e < Cout) {
-      float bv = 0.f;
-      bv = split_sum(a.bpart + e, (size_t)Cout, splits);
-      a.gbias[e] = a.wacc ? a.gbias[e] + bv : bv;
-    }
-  }
 }
 
 // dW[o][c][tap] = sum_s part[s][o][tap*Cin + c]; db[o] = sum_s part[s][o][NK].
@@ -2230,63 +1985,27 @@ WgPlan plan_wgrad(int Cin, int Cout, int T, long long P) {
   return pl;
 }
 
-// halo weight gradient: (KH, KW) in {1x5, 5x1, 3x3}
+// halo weight gradient (wgrad2_kernel): (KH, KW) in {1x1, 1x5, 5x1, 3x3} (`ok`,
+// which also decides whether the backward folds the activation into the
+// kernel).  64 x 64 channel tiles, one block of 8 waves per CU (85 KB LDS);
+// splits fill ~`target` blocks with >= `min_tiles` pixel tiles per split (each
+// split writes a full Cout x Cin x T partial).  The pixel tiles run over the
+// `nuse` uses of the weight (1 for a single convolution) x images x tiles.
 struct WhPlan {
   bool ok;
   int otiles, ctiles, tiles_x, tiles_img, splits, tiles_per_split;
   size_t part_bytes;
-  int tgroups;   // wgrad2, 3x3: blocks per (o, c) tile along the kernel rows (1 or 3)
+  int tgroups;   // 3x3: blocks per (o, c) tile along the kernel rows (1 or 3)
 };
 
-WhPlan plan_wgrad_halo(int Cin, int Cout, int KH, int KW, int B, int H, int W) {
+WhPlan plan_wgrad2(int Cin, int Cout, int KH, int KW, int nuse, int B, int H, int W) {
   WhPlan pl = {};
   pl.ok = (KH == 1 && KW == 5) || (KH == 5 && KW == 1) || (KH == 3 && KW == 3) || (KH == 1 && KW == 1);
   if (!pl.ok) return pl;
   const int TH = (KW == 1 || (KH == 3 && KW == 3)) ? 8 : 4, TW = 64 / TH;
   pl.tiles_x = (W + TW - 1) / TW;
   pl.tiles_img = ((H + TH - 1) / TH) * pl.tiles_x;
-  const int ntiles = B * pl.tiles_img;
-  pl.otiles = (Cout + 63) / 64;
-  pl.ctiles = (Cin + 31) / 32;
-  const int blocks = pl.otiles * pl.ctiles;
-  // ~1.5 blocks per CU (parallelism beats the partials' extra traffic here)
-  static const int max_sp = [] {   // tuning override: DRO_WH_MAX_SPLITS (default 32)
-    const char* e = getenv("DRO_WH_MAX_SPLITS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 32;
-  }();
-  static const int target = [] {   // tuning override: DRO_WH_TARGET_BLOCKS (default 384)
-    const char* e = getenv("DRO_WH_TARGET_BLOCKS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 384;
-  }();
-  int sp = (target + blocks - 1) / blocks;
-  if (sp > max_sp) sp = max_sp;
-  if (sp > ntiles) sp = ntiles;
-  if (sp < 1) sp = 1;
-  pl.tiles_per_split = (ntiles + sp - 1) / sp;
-  pl.splits = (ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-  pl.part_bytes = align256((size_t)pl.splits * Cout * Cin * KH * KW * sizeof(float)) +
-                  align256((size_t)pl.splits * Cout * sizeof(float));
-  return pl;
-}
-
-// weight gradient v2 (wgrad2_kernel): 64 x 64 channel tiles, one block of 8
-// waves per CU (85 KB LDS); splits fill ~`target` blocks with >= `min_tiles`
-// pixel tiles per split (each split writes a full Cout x Cin x T partial).  DRO_WGRAD_V1=1 keeps the wgrad_halo_kernel path (A/B).
-bool wgrad_v1() {
-  static const bool v1 = getenv("DRO_WGRAD_V1") != nullptr;
-  return v1;
-}
-
-WhPlan plan_wgrad2(int Cin, int Cout, int KH, int KW, int ntiles_total, int B, int H, int W) {
-  WhPlan pl = {};
-  pl.ok = (KH == 1 && KW == 5) || (KH == 5 && KW == 1) || (KH == 3 && KW == 3) || (KH == 1 && KW == 1);
-  if (!pl.ok) return pl;
-  const int TH = (KW == 1 || (KH == 3 && KW == 3)) ? 8 : 4, TW = 64 / TH;
-  pl.tiles_x = (W + TW - 1) / TW;
-  pl.tiles_img = ((H + TH - 1) / TH) * pl.tiles_x;
-  const int ntiles = ntiles_total > 0 ? ntiles_total : B * pl.tiles_img;
+  const int ntiles = nuse * B * pl.tiles_img;
   pl.otiles = (Cout + 63) / 64;
   pl.ctiles = (Cin + 63) / 64;
   // 3x3: one block per kernel row of a tile -- 3x the blocks at the same
@@ -2331,9 +2050,8 @@ size_t bwd_workspace(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
   return align256((size_t)Cout * P * sizeof(float)) +              // pre-activation gradient
          std::max(plan_igemm(Cin, Cout, KH, KW, B, H, W, Cin).part_bytes,  // data-gradient split-K
                   xconv_part_bytes(Cin, Cout, KH, KW, B, H, W)) +
-         std::max(std::max(plan_wgrad(Cin, Cout, T, P).part_bytes,  // weight-gradient partials
-                           plan_wgrad_halo(Cin, Cout, KH, KW, B, H, W).part_bytes),
-                  plan_wgrad2(Cin, Cout, KH, KW, 0, B, H, W).part_bytes);
+         std::max(plan_wgrad(Cin, Cout, T, P).part_bytes,                   // weight-gradient partials
+                  plan_wgrad2(Cin, Cout, KH, KW, 1, B, H, W).part_bytes);
 }
 
 bool too_big(long long B, long long C, long long HW) { return B * C * HW >= (1LL << 30); }
@@ -3399,7 +3117,7 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
                                  xconv_part_bytes(a.g.Cin, Cout, KH, KW, B, H, W));
   // fold the activation derivative into the halo kernels' G staging when both
   // gradients run there (dense y); otherwise form G first
-  const WhPlan wh = plan_wgrad_halo(a.g.Cin, Cout, KH, KW, B, H, W);
+  const WhPlan wh = plan_wgrad2(a.g.Cin, Cout, KH, KW, 1, B, H, W);
   const bool halo_dgrad = plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W, a.g.Cin).halo;
   // the thin data gradient (7x7 over <= 8 input channels, one source) folds
   // as well; a call without a weight gradient (the trainer queues those)
@@ -3437,50 +3155,27 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
       DRO_ACT_SWITCH(gact, st = (launch_igemm<1, A_, 0>(a, P, ws_ig, s)));
     if (st) return st;
   }
-  if (grad_weight && wh.ok && !wgrad_v1()) {
-    const WhPlan w2 = plan_wgrad2(a.g.Cin, Cout, KH, KW, 0, B, H, W);
-    a.otiles = w2.otiles;
-    a.tiles_x = w2.tiles_x;
-    a.tiles_img = w2.tiles_img;
-    a.chunks_per_split = w2.tiles_per_split;
-    a.part = reinterpret_cast<float*>(ws_wg);
-    a.bpart = reinterpret_cast<float*>(ws_wg + align256((size_t)w2.splits * Cout * a.g.Cin * T * sizeof(float)));
-    const dim3 grid((unsigned)(w2.otiles * w2.ctiles * w2.tgroups), (unsigned)w2.splits);
-    const int gact = fold ? act : 0;
-    conv_logf(2.0 * Cout * a.g.Cin * T * (double)P, "wgrad2_kernel<%d, %d, %d, false, %d>", KH, KW, gact,
-              w2.tgroups);
-#define DRO_WG2(KH_, KW_, TG_) DRO_ACT_SWITCH(gact, hipLaunchKernelGGL((wgrad2_kernel<KH_, KW_, A_, false, TG_>), grid, dim3(512), 0, s, a))
-    if (KH == 1 && KW == 1) { DRO_WG2(1, 1, 1); }
-    else if (KH == 1) { DRO_WG2(1, 5, 1); }
-    else if (KW == 1) { DRO_WG2(5, 1, 1); }
-    else if (w2.tgroups == 3) { DRO_WG2(3, 3, 3); }
-    else { DRO_WG2(3, 3, 1); }
-#undef DRO_WG2
-    if ((st = launch_status("wgrad2_kernel launch failed"))) return st;
-    launch_wgrad2_finish(a, w2.splits, s);
-    if ((st = launch_status("wgrad_halo_finish_kernel launch failed"))) return st;
-  } else if (grad_weight && wh.ok) {
+  if (grad_weight && wh.ok) {
     a.otiles = wh.otiles;
     a.tiles_x = wh.tiles_x;
     a.tiles_img = wh.tiles_img;
     a.chunks_per_split = wh.tiles_per_split;
     a.part = reinterpret_cast<float*>(ws_wg);
     a.bpart = reinterpret_cast<float*>(ws_wg + align256((size_t)wh.splits * Cout * a.g.Cin * T * sizeof(float)));
-    const dim3 grid((unsigned)(wh.otiles * wh.ctiles), (unsigned)wh.splits);
+    const dim3 grid((unsigned)(wh.otiles * wh.ctiles * wh.tgroups), (unsigned)wh.splits);
     const int gact = fold ? act : 0;
-    conv_logf(2.0 * Cout * a.g.Cin * T * (double)P, "wgrad_halo_kernel<%d, %d, %d, false>", KH, KW, gact);
-#define DRO_WH(KH_, KW_) DRO_ACT_SWITCH(gact, hipLaunchKernelGGL((wgrad_halo_kernel<KH_, KW_, A_, false>), grid, dim3(256), 0, s, a))
-    if (KH == 1 && KW == 1) { DRO_WH(1, 1); }
-    else if (KH == 1) { DRO_WH(1, 5); }
-    else if (KW == 1) { DRO_WH(5, 1); }
-    else { DRO_WH(3, 3); }
-#undef DRO_WH
-    if ((st = launch_status("wgrad_halo_kernel launch failed"))) return st;
-    const long long total = (long long)Cout * a.g.Cin * T;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(wgrad_halo_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, wh.splits);
-    if ((st = launch_status("wgrad_halo_finish_kernel launch failed"))) return st;
+    conv_logf(2.0 * Cout * a.g.Cin * T * (double)P, "wgrad2_kernel<%d, %d, %d, false, %d>", KH, KW, gact,
+              wh.tgroups);
+#define DRO_WG2(KH_, KW_, TG_) DRO_ACT_SWITCH(gact, hipLaunchKernelGGL((wgrad2_kernel<KH_, KW_, A_, false, TG_>), grid, dim3(512), 0, s, a))
+    if (KH == 1 && KW == 1) { DRO_WG2(1, 1, 1); }
+    else if (KH == 1) { DRO_WG2(1, 5, 1); }
+    else if (KW == 1) { DRO_WG2(5, 1, 1); }
+    else if (wh.tgroups == 3) { DRO_WG2(3, 3, 3); }
+    else { DRO_WG2(3, 3, 1); }
+#undef DRO_WG2
+    if ((st = launch_status("wgrad2_kernel launch failed"))) return st;
+    launch_wgrad2_finish(a, wh.splits, s);
+    if ((st = launch_status("wgrad2_finish_kernel launch failed"))) return st;
   } else if (grad_weight) {
     const WgPlan pl = plan_wgrad(a.g.Cin, Cout, T, P);
     a.K = a.g.Cin * T;
@@ -3822,42 +3517,11 @@ extern "C" int dro_conv2d_strided_backward(const float* x, const float* weight, 
 }
 
 // ------------------------------------------------------------------ batched weight gradient (host)
-// Split policy for a whole training step's uses of one weight: ~2 blocks per
-// CU, at least 4 pixel tiles per split, at most 64 splits.
-static WhPlan plan_wgrad_multi(int Cin, int Cout, int KH, int KW, int nuse, int B, int H, int W) {
-  WhPlan pl = plan_wgrad_halo(Cin, Cout, KH, KW, B, H, W);
-  if (!pl.ok) return pl;
-  const int ntiles = nuse * B * pl.tiles_img;
-  const int blocks = pl.otiles * pl.ctiles;
-  static const int target = [] {   // tuning override: DRO_WHM_TARGET_BLOCKS (default 512)
-    const char* e = getenv("DRO_WHM_TARGET_BLOCKS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 512;
-  }();
-  static const int max_sp = [] {   // tuning override: DRO_WHM_MAX_SPLITS (default 64)
-    const char* e = getenv("DRO_WHM_MAX_SPLITS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : 64;
-  }();
-  int sp = (target + blocks - 1) / blocks;
-  if (sp > max_sp) sp = max_sp;
-  if (sp > ntiles / 4) sp = ntiles / 4;
-  if (sp < 1) sp = 1;
-  pl.tiles_per_split = (ntiles + sp - 1) / sp;
-  pl.splits = (ntiles + pl.tiles_per_split - 1) / pl.tiles_per_split;
-  pl.part_bytes = align256((size_t)pl.splits * Cout * Cin * KH * KW * sizeof(float)) +
-                  align256((size_t)pl.splits * Cout * sizeof(float));
-  return pl;
-}
 
 extern "C" size_t dro_conv2d_weight_grad_multi_workspace_bytes(int nuse, int B, int H, int W, int Cin,
                                                               int Cout, int KH, int KW) {
   if (nuse < 1) nuse = 1;
-  if (!wgrad_v1()) {
-    const WhPlan t = plan_wgrad_halo(Cin, Cout, KH, KW, B, H, W);
-    return plan_wgrad2(Cin, Cout, KH, KW, nuse * B * t.tiles_img, B, H, W).part_bytes;
-  }
-  return plan_wgrad_multi(Cin, Cout, KH, KW, nuse, B, H, W).part_bytes;
+  return plan_wgrad2(Cin, Cout, KH, KW, nuse, B, H, W).part_bytes;
 }
 
 extern "C" int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse, int nsrc, int B, int H,
@@ -3899,10 +3563,7 @@ extern "C" int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse,
     m.uy[u] = act ? uses[u].y : nullptr;
   }
   const int Cin = m.a.g.Cin, T = KH * KW;
-  const bool v2 = !wgrad_v1();
-  const int ntiles_all = nuse * B * plan_wgrad_halo(Cin, Cout, KH, KW, B, H, W).tiles_img;
-  const WhPlan wh = v2 ? plan_wgrad2(Cin, Cout, KH, KW, ntiles_all, B, H, W)
-                       : plan_wgrad_multi(Cin, Cout, KH, KW, nuse, B, H, W);
+  const WhPlan wh = plan_wgrad2(Cin, Cout, KH, KW, nuse, B, H, W);
   if (!wh.ok) {
     set_error("conv2d_weight_grad_multi: kernel shape not supported (1x1, 1x5, 5x1, 3x3)");
     return DRO_E_SHAPE;
@@ -3924,46 +3585,21 @@ extern "C" int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse,
   a.bpart = reinterpret_cast<float*>(ws + align256((size_t)wh.splits * Cout * Cin * T * sizeof(float)));
   m.nuse = nuse;
   m.use_tiles = B * wh.tiles_img;
-  a.stamps = g_conv_stamps;
-  a.dbg = 0;
-  if (g_conv_stamps) {
-    const char* e = getenv("DRO_CONV_DBG");
-    a.dbg = e ? atoi(e) : 0;
-  }
   hipStream_t s = (hipStream_t)stream;
-  const int tgroups = v2 ? wh.tgroups : 1;
+  const int tgroups = wh.tgroups;
   const dim3 grid((unsigned)(wh.otiles * wh.ctiles * tgroups), (unsigned)wh.splits);
-  if (v2)
-    conv_logf(2.0 * Cout * Cin * T * (double)B * H * W * nuse, "wgrad2_kernel<%d, %d, %d, true, %d>", KH, KW,
-              act, tgroups);
-  else
-    conv_logf(2.0 * Cout * Cin * T * (double)B * H * W * nuse, "wgrad_halo_kernel<%d, %d, %d, true>", KH, KW,
-              act);
-  if (v2) {
+  conv_logf(2.0 * Cout * Cin * T * (double)B * H * W * nuse, "wgrad2_kernel<%d, %d, %d, true, %d>", KH, KW,
+            act, tgroups);
 #define DRO_WG2M(KH_, KW_, TG_) DRO_ACT_SWITCH(act, hipLaunchKernelGGL((wgrad2_kernel<KH_, KW_, A_, true, TG_>), grid, dim3(512), 0, s, m))
-    if (KH == 1 && KW == 1) { DRO_WG2M(1, 1, 1); }
-    else if (KH == 1) { DRO_WG2M(1, 5, 1); }
-    else if (KW == 1) { DRO_WG2M(5, 1, 1); }
-    else if (tgroups == 3) { DRO_WG2M(3, 3, 3); }
-    else { DRO_WG2M(3, 3, 1); }
+  if (KH == 1 && KW == 1) { DRO_WG2M(1, 1, 1); }
+  else if (KH == 1) { DRO_WG2M(1, 5, 1); }
+  else if (KW == 1) { DRO_WG2M(5, 1, 1); }
+  else if (tgroups == 3) { DRO_WG2M(3, 3, 3); }
+  else { DRO_WG2M(3, 3, 1); }
 #undef DRO_WG2M
-  } else {
-#define DRO_WHM(KH_, KW_) DRO_ACT_SWITCH(act, hipLaunchKernelGGL((wgrad_halo_kernel<KH_, KW_, A_, true>), grid, dim3(256), 0, s, m))
-    if (KH == 1 && KW == 1) { DRO_WHM(1, 1); }
-    else if (KH == 1) { DRO_WHM(1, 5); }
-    else if (KW == 1) { DRO_WHM(5, 1); }
-    else { DRO_WHM(3, 3); }
-#undef DRO_WHM
-  }
-  if ((st = launch_status("wgrad_halo_kernel<multi> launch failed"))) return st;
-  const long long total = (long long)Cout * Cin * T;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  if (v2)
-    launch_wgrad2_finish(a, wh.splits, s);
-  else
-    hipLaunchKernelGGL(wgrad_halo_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, wh.splits);
-  return launch_status("wgrad_halo_finish_kernel launch failed");
+  if ((st = launch_status("wgrad2_kernel<multi> launch failed"))) return st;
+  launch_wgrad2_finish(a, wh.splits, s);
+  return launch_status("wgrad2_finish_kernel launch failed");
 }
 
 // ------------------------------------------------------------------ grouped weight gradient (host)

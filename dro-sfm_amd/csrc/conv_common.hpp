@@ -169,9 +169,9 @@ struct IgArgs {
 };
 
 // The K-loop ablations exist only in a diagnostic build (-DDRO_CONV_ABLATE=1,
-// for tools/conv_stamps.py and tools/wgrad_stamps.py): in the product build
-// the flags fold to 0.  A runtime ablation branch cost the weight-gradient
-// kernel its full unroll (1x5 multi-use launch 123 -> 176 us).
+// for tools/conv_stamps.py): in the product build the flags fold to 0.  A
+// runtime ablation branch cost the weight-gradient kernel its full unroll
+// (1x5 multi-use launch 123 -> 176 us).
 #ifndef DRO_CONV_ABLATE
 #define DRO_CONV_ABLATE 0
 #endif

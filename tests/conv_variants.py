@@ -223,7 +223,7 @@ D, S, BC = "dense", "slice", "bcast"
 #   2 x 61 x 237 -> 480 (both)   2 x 61 x 250 -> 512 (both)
 CASES = [
     # ---- 3x3 halo kernel: CK 8 (BM 32) / 4 (BM 64)
-    _conv("c33_bm32_k4", [(D, 28)], 30, (3, 3), "relu", 2, 19, 45, H(32, 4), H(32, 4), subsets=("wgradv1",)),
+    _conv("c33_bm32_k4", [(D, 28)], 30, (3, 3), "relu", 2, 19, 45, H(32, 4), H(32, 4)),
     _conv("c33_bm32_k4_none", [(S, 28)], 30, (3, 3), None, 2, 19, 45, H(32, 4), H(32, 4)),
     _conv("c33_bm32_k2", [(D, 20), (S, 8)], 30, (3, 3), "relu", 3, 37, 150, H(32, 2), H(32, 2)),
     _conv("c33_bm32_k2_none", [(D, 28)], 30, (3, 3), None, 3, 37, 150, H(32, 2), H(32, 2)),
@@ -236,8 +236,8 @@ CASES = [
     # 9 / 10 chunks over kin 4 x ksplit 2: splits of 5 + 4 chunks, the last wave group short
     _conv("c33_split", [(D, 68)], 74, (3, 3), None, 1, 13, 21, H(32, 4, True), H(32, 4, True)),
     # the heads: few output channels (forward kin 4), many input channels (data gradient kin 1)
-    _conv("c33_head_sigmoid", [(D, 68)], 3, (3, 3), "sigmoid", 2, 37, 150, H(32, 4), H(32, 1), subsets=("wgradv1",)),
-    _conv("c33_head_tanh", [(S, 68)], 1, (3, 3), "tanh", 2, 37, 150, H(32, 4), H(32, 1), subsets=("wgradv1",)),
+    _conv("c33_head_sigmoid", [(D, 68)], 3, (3, 3), "sigmoid", 2, 37, 150, H(32, 4), H(32, 1)),
+    _conv("c33_head_tanh", [(S, 68)], 1, (3, 3), "tanh", 2, 37, 150, H(32, 4), H(32, 1)),
     # weight rows [Cin][T] whose length is no multiple of 4 go to the flat kernel (the
     # halo kernel's 16-byte weight runs would straddle the end of the tensor), whether
     # or not the whole tensor's count is one
@@ -248,21 +248,21 @@ CASES = [
     # ---- 1x5 halo kernel: CK 16 (BM 32) / 8 (BM 64), tiles 4 x 16
     # (every kin > 1 case has, in the forward or the data gradient, a chunk count
     # that puts the last, partial chunk into the last wave group)
-    _conv("c15_bm32_k4", [(D, 30), (S, 22)], 56, (1, 5), None, 2, 13, 37, H(32, 4), H(32, 4), subsets=("wgradv1",)),
+    _conv("c15_bm32_k4", [(D, 30), (S, 22)], 56, (1, 5), None, 2, 13, 37, H(32, 4), H(32, 4)),
     _conv("c15_bm32_k2", [(D, 20)], 22, (1, 5), None, 2, 37, 230, H(32, 2), H(32, 2)),
     _conv("c15_bm32_k1", [(S, 40)], 45, (1, 5), None, 2, 37, 230, H(32, 1), H(32, 1)),
     _conv("c15_bm64_k2", [(D, 20)], 28, (1, 5), "sigmoid", 2, 61, 237, H(64, 2), H(64, 2)),
     _conv("c15_bm64_k1", [(D, 14), (BC, 6)], 22, (1, 5), None, 2, 61, 250, H(64, 1), H(64, 1)),
     _conv("c15_split", [(D, 132)], 136, (1, 5), None, 1, 13, 37, H(32, 4, True), H(32, 4, True)),
     # ---- 5x1 halo kernel: CK 16 / 8, tiles 8 x 8
-    _conv("c51_bm32_k4", [(D, 30), (S, 22)], 56, (5, 1), None, 2, 19, 45, H(32, 4), H(32, 4), subsets=("wgradv1",)),
+    _conv("c51_bm32_k4", [(D, 30), (S, 22)], 56, (5, 1), None, 2, 19, 45, H(32, 4), H(32, 4)),
     _conv("c51_bm32_k2", [(D, 20)], 22, (5, 1), None, 3, 37, 150, H(32, 2), H(32, 2)),
     _conv("c51_bm32_k1", [(S, 40)], 45, (5, 1), None, 3, 37, 150, H(32, 1), H(32, 1)),
     _conv("c51_bm64_k2", [(D, 20)], 28, (5, 1), "tanh", 2, 61, 237, H(64, 2), H(64, 2)),
     _conv("c51_bm64_k1", [(D, 14), (BC, 6)], 22, (5, 1), None, 2, 61, 250, H(64, 1), H(64, 1)),
     _conv("c51_split", [(D, 132)], 136, (5, 1), None, 1, 13, 21, H(32, 4, True), H(32, 4, True)),
     # ---- 1x1 halo kernel: CK 32 / 16
-    _conv("c11_bm32_k4", [(D, 100)], 104, (1, 1), "relu", 2, 19, 45, H(32, 4), H(32, 4), subsets=("wgradv1",)),
+    _conv("c11_bm32_k4", [(D, 100)], 104, (1, 1), "relu", 2, 19, 45, H(32, 4), H(32, 4)),
     _conv("c11_bm32_k4_mask", [(S, 100)], 104, (1, 1), None, 2, 19, 45, H(32, 4), H(32, 4), alpha=0.25),
     _conv("c11_bm32_k2", [(D, 40)], 45, (1, 1), "relu", 2, 37, 150, H(32, 2), H(32, 2)),
     _conv("c11_bm32_k2_none", [(S, 40)], 45, (1, 1), None, 2, 37, 150, H(32, 2), H(32, 2)),
@@ -341,12 +341,6 @@ assert len(BY_NAME) == len(CASES)
 # its subset runs (tests/test_conv_toggles.py)
 TOGGLES = {
     "k7fwd": ("DRO_K7_FWD", ["fwd_k7s2_kernel<3>", "fwd_k7s2_kernel<6>"], []),
-    "wgradv1": ("DRO_WGRAD_V1", ["wgrad_halo_kernel<3, 3, 1, false>", "wgrad_halo_kernel<3, 3, 1, true>",
-                                 "wgrad_halo_kernel<3, 3, 2, false>", "wgrad_halo_kernel<3, 3, 3, true>",
-                                 "wgrad_halo_kernel<1, 5, 0, false>", "wgrad_halo_kernel<1, 5, 0, true>",
-                                 "wgrad_halo_kernel<5, 1, 0, false>", "wgrad_halo_kernel<5, 1, 0, true>",
-                                 "wgrad_halo_kernel<1, 1, 1, false>", "wgrad_halo_kernel<1, 1, 1, true>"],
-                ["wgrad2_kernel"]),
     "k7wgradoff": ("DRO_K7_WGRAD_OFF", ["wgrad_kernel("], ["wgrad_k7_kernel"]),
     "nothin": ("DRO_CONV_NO_THIN", ["igemm_kernel<32, 0, 1, 0>", "igemm_kernel<32, 1, 0, 0>", "igemm_kernel<32, 0, 0, 0>"],
                ["thin_fwd_kernel", "thin_dgrad_kernel"]),

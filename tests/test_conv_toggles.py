@@ -1,8 +1,8 @@
 """The conv-engine kernels behind process-wide switches of libdro_amd.so.
 
-DRO_K7_FWD (fwd_k7s2_kernel), DRO_WGRAD_V1 (wgrad_halo_kernel),
-DRO_K7_WGRAD_OFF (the 7x7 weight gradients on wgrad_kernel) and
-DRO_CONV_NO_THIN (the thin 7x7 shapes on igemm_kernel) are each read once into
+DRO_K7_FWD (fwd_k7s2_kernel), DRO_K7_WGRAD_OFF (the 7x7 weight gradients on
+wgrad_kernel) and DRO_CONV_NO_THIN (the thin 7x7 shapes on igemm_kernel) are
+each read once into
 a static, so the suite's own process never takes the other branch.  Each
 switch gets one fresh child process (python -m tests.conv_variants --subset
 NAME) that runs the table cases the switch re-routes with the same fp64
@@ -21,7 +21,7 @@ import conv_variants as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT = 240          # seconds per child: import + a handful of small cases
-ORDER = ["k7fwd", "wgradv1", "k7wgradoff", "nothin"]
+ORDER = ["k7fwd", "k7wgradoff", "nothin"]
 _RESULTS = {}
 
 

@@ -105,6 +105,26 @@ def test_table_is_ragged():
                 assert -(-kch // ck) % (p.kin * 2), (c.name, label)
 
 
+# (nuse, B, H, W, Cin, Cout, KH, KW) -> (splits, bytes): the halo weight
+# gradient's split plan (csrc/conv.hip plan_wgrad2), one shape per clamp;
+# bytes = align256(splits * Cout * Cin * KH * KW * 4) + align256(splits * Cout * 4)
+WGRAD_PLAN_PINS = [
+    ((1, 6, 48, 160, 64, 64, 3, 3), 240, 35450880),     # the benchmark's roofline call: the 256-split cap
+    ((1, 2, 24, 80, 128, 128, 3, 3), 60, 35420160),     # tile-count bound
+    ((1, 2, 24, 80, 256, 256, 1, 1), 15, 3947520),      # block-target bound
+    ((8, 2, 24, 80, 256, 128, 1, 5), 32, 20987904),     # multi-use: tiles over (use, image, tile)
+]
+
+
+def test_wgrad_multi_workspace_pinned(lib):
+    def align256(n):
+        return (n + 255) // 256 * 256
+    for shape, splits, nbytes in WGRAD_PLAN_PINS:
+        nuse, B, H, W, Cin, Cout, KH, KW = shape
+        assert nbytes == align256(splits * Cout * Cin * KH * KW * 4) + align256(splits * Cout * 4), shape
+        assert lib.dro_conv2d_weight_grad_multi_workspace_bytes(*shape) == nbytes, shape
+
+
 # ------------------------------------------------------------------ parity (GPU)
 def _engines(c):
     """Both engines where the split-bf16 one (csrc/xconv.hip) takes the call."""
