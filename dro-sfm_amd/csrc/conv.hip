@@ -446,7 +446,8 @@ __global__ __launch_bounds__(256 * KS) void dconv_kernel(IgArgs a) {
   const int cb1 = a.cbase[1], cb2 = a.cbase[2], cb3 = a.cbase[3];
   const int H = a.g.H, W = a.g.W;
   const int Cin = a.g.Cin, Cout = a.g.Cout, rows = a.rows, kch = a.kch;
-  const int CinT = Cin * T;
+  // weight row length: the data gradient may read a column range of a wider weight
+  const int CinT = (MODE == 1 ? a.wcin : Cin) * T;
   const float* __restrict__ Wt = a.weight;
   const float* __restrict__ Gp = a.G;
   const int tid = threadIdx.x & 255, lane = tid & 63;
@@ -456,6 +457,17 @@ __global__ __launch_bounds__(256 * KS) void dconv_kernel(IgArgs a) {
   const int tile = xcd_remap(blockIdx.x, gridDim.x);
   const int pt = (int)udiv((unsigned)tile, a.rt_div), rt = tile - pt * a.row_tiles;
   const int row0 = rt * BM;
+  if constexpr (MODE == 1 && XF == 0 && EPI < 5) {
+    // a row tile wholly inside one source that has no gradient target: nothing
+    // of it would be stored (block uniform, before the first barrier)
+    const int rl = min(row0 + BM, rows) - 1;
+    const int s0 = (row0 >= cb1) + (row0 >= cb2) + (row0 >= cb3);
+    const int s1 = (rl >= cb1) + (rl >= cb2) + (rl >= cb3);
+    const float* t0 = s0 == 0 ? a.gsrc[0] : s0 == 1 ? a.gsrc[1] : s0 == 2 ? a.gsrc[2] : a.gsrc[3];
+    if (s0 == s1 && t0 == nullptr) return;
+  }
+  // first weight column of this row tile (MODE 1)
+  const int wcol0 = MODE == 1 ? row0 + (row0 >= a.wgap_at ? a.wgap_len : 0) : row0;
   const int b = (int)udiv((unsigned)pt, a.ti_div), trem = pt - b * a.tiles_img;
   const int tyi = (int)udiv((unsigned)trem, a.tx_div);
   const int ty0 = tyi * TH, tx0 = (trem - tyi * a.tiles_x) * TW;
@@ -557,7 +569,7 @@ __global__ __launch_bounds__(256 * KS) void dconv_kernel(IgArgs a) {
   constexpr int NVM = WPER4 + XPER * NJ;
   auto prep = [&](Stage& st, int chunk, Rows& r) {
     const int c0 = chunk * CK;
-    r.gbase = MODE == 0 ? (unsigned)row0 * CinT + (unsigned)c0 * T : (unsigned)c0 * CinT + (unsigned)row0 * T;
+    r.gbase = MODE == 0 ? (unsigned)row0 * CinT + (unsigned)c0 * T : (unsigned)c0 * CinT + (unsigned)wcol0 * T;
     unsigned cm = 0;
 #pragma unroll
     for (int i = 0; i < XPER; ++i) {
@@ -1313,6 +1325,7 @@ struct WgGroupMember {
   int use0;               // first use slot
   int block0, fin0, fin_blocks;   // first block in the main and the finish grid, finish blocks
   int finish_q, wacc;
+  int wcin, gap_at, gap_len;      // the weight's row length and column gap (WgFinish)
   float galpha;
   float* part;            // [splits][T][Cout][Cin]
   float* bpart;           // [splits][Cout]
@@ -1397,6 +1410,10 @@ struct WgFinish {         // one weight's partials and targets; block `block` of
   float* gweight;
   float* gbias;
   int wacc, Cout, Cin, T, splits, block, nblocks;
+  // the partials' Cin channels are the columns of a wider weight [Cout][wcin][T]
+  // but [gap_at, gap_at + gap_len): channel c goes to column c + (c >= gap_at ?
+  // gap_len : 0).  wcin = Cin, gap_len = 0: the weight as it is
+  int wcin, gap_at, gap_len;
 };
 
 template <int Q>
@@ -1423,7 +1440,11 @@ __device__ __forceinline__ void wgrad2_finish_block(const WgFinish& a) {
     if (ok && q == 0) {
       const int tap = (int)(e / oc);
       const long long r = e - (long long)tap * oc;        // o * Cin + c
-      const size_t dst = (size_t)r * T + tap;
+      size_t dst = (size_t)r * T + tap;
+      if (a.wcin != Cin) {
+        const int o = (int)(r / Cin), c = (int)(r - (long long)o * Cin);
+        dst = ((size_t)o * a.wcin + c + (c >= a.gap_at ? a.gap_len : 0)) * T + tap;
+      }
       a.gweight[dst] = a.wacc ? a.gweight[dst] + v : v;
     }
   }
@@ -1441,6 +1462,7 @@ __global__ __launch_bounds__(256) void wgrad2_finish_kernel(IgArgs a, int splits
   f.part = a.part, f.bpart = a.bpart, f.gweight = a.gweight, f.gbias = a.gbias, f.wacc = a.wacc;
   f.Cout = a.g.Cout, f.Cin = a.g.Cin, f.T = a.g.KH * a.g.KW, f.splits = splits;
   f.block = (int)blockIdx.x, f.nblocks = (int)gridDim.x;
+  f.wcin = a.wcin ? a.wcin : a.g.Cin, f.gap_at = a.wgap_at, f.gap_len = a.wgap_len;
   wgrad2_finish_block<Q>(f);
 }
 
@@ -1454,6 +1476,7 @@ __global__ __launch_bounds__(256) void wgrad2_group_finish_kernel(WgGroupHead P)
   f.part = km->part, f.bpart = km->bpart, f.gweight = km->gweight, f.gbias = km->gbias, f.wacc = km->wacc;
   f.Cout = km->Cout, f.Cin = km->Cin, f.T = P.T, f.splits = km->splits;
   f.block = id - km->fin0, f.nblocks = km->fin_blocks;
+  f.wcin = km->wcin, f.gap_at = km->gap_at, f.gap_len = km->gap_len;
   const int Q = km->finish_q;
   if (Q == 4) wgrad2_finish_block<4>(f);
   else if (Q == 2) wgrad2_finish_block<2>(f);
@@ -2438,8 +2461,13 @@ unsigned long long* g_conv_stamps = nullptr;   // dro_debug_conv_stamps
 // rows / kch set by the caller; `ws` must hold plan.part_bytes
 template <int MODE, int ACT, int EPI, int XF = 0>
 int launch_igemm(IgArgs& a, long long P, char* ws, hipStream_t s) {
+  const bool gapped = MODE == 1 && a.wcin != 0;   // (conv2d_backward_impl checked that the halo kernel runs it)
+  if (!gapped) {
+    a.wcin = a.g.Cin;
+    a.wgap_at = a.wgap_len = 0;
+  }
   IgPlan pl = a.flat_only ? plan_igemm_flat(a.rows, a.kch, a.g.KH, a.g.KW, a.g.B, a.g.H, a.g.W)
-                          : plan_igemm(a.rows, a.kch, a.g.KH, a.g.KW, a.g.B, a.g.H, a.g.W, a.g.Cin);
+                          : plan_igemm(a.rows, a.kch, a.g.KH, a.g.KW, a.g.B, a.g.H, a.g.W, a.wcin);
   // BN fused into the conv (BnFuse): 3x3 halo kernel only, and no split-K for
   // the statistics epilogues (the blocks' own tiles are the partials)
   constexpr bool BNF = EPI >= 5 || XF != 0;
@@ -3025,16 +3053,36 @@ struct GruFold {
   int dh_acc;
 };
 
+struct WeightGap {   // dro_conv2d_backward_gapped
+  int wcin, gap_at, gap_len;
+};
+
 static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* weight, int B, int H, int W,
                                 int Cout, int KH, int KW, int act, float alpha, const dro_slice* y,
                                 const float* dout, float* const* grad_srcs, const int* grad_ctot,
                                 const int* grad_coff, const int* grad_accumulate, float* grad_weight,
                                 float* grad_bias, int grad_weight_accumulate, const void* wsplit,
-                                void* workspace, size_t workspace_bytes, void* stream, const GruFold* gf) {
+                                void* workspace, size_t workspace_bytes, void* stream, const GruFold* gf,
+                                const WeightGap* gap = nullptr) {
   IgArgs a = {};
   a.wsplit = static_cast<const char*>(wsplit);   // transposed layout: the data gradient
   int st = conv_setup_geom(a, srcs, nsrc, B, H, W, Cout, KH, KW);
   if (st) return st;
+  if (gap) {
+    // the sources cover the weight's columns but [gap_at, gap_at + gap_len): data
+    // gradient only, on the halo kernel (the only one that knows the gap)
+    const IgPlan gp = plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W, gap->wcin);
+    const long long T = (long long)KH * KW;
+    if (gap->gap_at < 0 || gap->gap_len < 0 || gap->gap_at > a.g.Cin || a.g.Cin + gap->gap_len > gap->wcin ||
+        grad_weight || wsplit || gf || !gp.halo || gap->gap_at % gp.bm != 0 || (gap->gap_len * T) % 4 != 0) {
+      set_error("conv2d_backward_gapped: needs a halo-kernel data gradient (1x1, 1x5, 5x1, 3x3; weight rows "
+                "and the gap multiples of 4 floats), the gap at a row-tile boundary inside the weight row");
+      return DRO_E_SHAPE;
+    }
+    a.wcin = gap->wcin;
+    a.wgap_at = gap->gap_at;
+    a.wgap_len = gap->gap_len;
+  }
   const bool pre = act != 0 || alpha != 1.f;
   if (!weight || !dout || (act != 0 && (!y || !y->data))) {
     set_error("conv2d_backward: NULL weight/dout/y");
@@ -3209,6 +3257,18 @@ extern "C" int dro_conv2d_backward(const dro_slice* srcs, int nsrc, const float*
   return conv2d_backward_impl(srcs, nsrc, weight, B, H, W, Cout, KH, KW, act, alpha, y, dout, grad_srcs,
                               grad_ctot, grad_coff, grad_accumulate, grad_weight, grad_bias,
                               grad_weight_accumulate, wsplit, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int dro_conv2d_backward_gapped(const dro_slice* srcs, int nsrc, const float* weight, int wcin,
+                                          int gap_at, int gap_len, int B, int H, int W, int Cout, int KH,
+                                          int KW, const float* dout, float* const* grad_srcs,
+                                          const int* grad_ctot, const int* grad_coff,
+                                          const int* grad_accumulate, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  const WeightGap gap = {wcin, gap_at, gap_len};
+  return conv2d_backward_impl(srcs, nsrc, weight, B, H, W, Cout, KH, KW, 0, 1.f, nullptr, dout, grad_srcs,
+                              grad_ctot, grad_coff, grad_accumulate, nullptr, nullptr, 0, nullptr, workspace,
+                              workspace_bytes, stream, nullptr, &gap);
 }
 
 extern "C" int dro_convgru_candidate_backward(const dro_slice* srcs, int nsrc, const float* weight, int B,
@@ -3524,10 +3584,25 @@ extern "C" size_t dro_conv2d_weight_grad_multi_workspace_bytes(int nuse, int B, 
   return plan_wgrad2(Cin, Cout, KH, KW, nuse, B, H, W).part_bytes;
 }
 
+// true when `gap` (nullable: none) places cin source channels inside a weight row
+static bool weight_gap_ok(const dro_wgrad_gap* gap, int cin) {
+  return !gap || (gap->gap_at >= 0 && gap->gap_len >= 0 && gap->gap_at <= cin &&
+                  (long long)cin + gap->gap_len <= gap->wcin);
+}
+
 extern "C" int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse, int nsrc, int B, int H,
                                             int W, int Cout, int KH, int KW, int act, float alpha,
                                             float* grad_weight, float* grad_bias, int accumulate,
                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return dro_conv2d_weight_grad_multi_ex(uses, nuse, nsrc, B, H, W, Cout, KH, KW, act, alpha, grad_weight,
+                                         grad_bias, accumulate, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dro_conv2d_weight_grad_multi_ex(const dro_wgrad_use* uses, int nuse, int nsrc, int B, int H,
+                                               int W, int Cout, int KH, int KW, int act, float alpha,
+                                               float* grad_weight, float* grad_bias, int accumulate,
+                                               const dro_wgrad_gap* gap, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
   if (!uses || !grad_weight) {
     set_error("conv2d_weight_grad_multi: NULL uses/grad_weight");
     return DRO_E_NULL;
@@ -3569,7 +3644,12 @@ extern "C" int dro_conv2d_weight_grad_multi(const dro_wgrad_use* uses, int nuse,
     return DRO_E_SHAPE;
   }
   if ((st = check_ws(workspace, workspace_bytes, wh.part_bytes, "conv2d_weight_grad_multi"))) return st;
+  if (!weight_gap_ok(gap, Cin)) {
+    set_error("conv2d_weight_grad_multi: the sources and the gap do not fit the weight row");
+    return DRO_E_SHAPE;
+  }
   IgArgs& a = m.a;
+  if (gap) a.wcin = gap->wcin, a.wgap_at = gap->gap_at, a.wgap_len = gap->gap_len;   // (the finish)
   a.G = uses[0].dout;
   a.gy = m.uy[0];
   a.galpha = alpha;
@@ -3608,8 +3688,8 @@ namespace {
 
 // Checks a group's members and plans the launch; with `g`, also fills the
 // kernel arguments except the workspace pointers.  Nothing is launched.
-int group_setup(const dro_wgrad_member* members, int nmember, int KH, int KW, int act, WgGroupPlan* pl,
-                WgGroup* g) {
+int group_setup(const dro_wgrad_member* members, const dro_wgrad_gap* gaps, int nmember, int KH, int KW,
+                int act, WgGroupPlan* pl, WgGroup* g) {
   if (!members) {
     set_error("conv2d_weight_grad_group: NULL members");
     return DRO_E_NULL;
@@ -3663,9 +3743,15 @@ int group_setup(const dro_wgrad_member* members, int nmember, int KH, int KW, in
       }
     }
     shapes[i] = {mb.nuse, mb.B, mb.H, mb.W, first.g.Cin, mb.Cout};
+    if (!weight_gap_ok(gaps ? gaps + i : nullptr, first.g.Cin)) {
+      set_error("conv2d_weight_grad_group: a member's sources and gap do not fit its weight row");
+      return DRO_E_SHAPE;
+    }
     if (g) {
       WgGroupMember& m = g->h.m[i];
       m.H = mb.H, m.W = mb.W, m.Cin = first.g.Cin, m.Cout = mb.Cout;
+      m.wcin = gaps ? gaps[i].wcin : first.g.Cin;
+      m.gap_at = gaps ? gaps[i].gap_at : 0, m.gap_len = gaps ? gaps[i].gap_len : 0;
       m.cb1 = first.cbase[1], m.cb2 = first.cbase[2], m.cb3 = first.cbase[3];
       m.galpha = mb.alpha;
       m.gweight = mb.grad_weight;
@@ -3697,15 +3783,22 @@ extern "C" int dro_conv2d_weight_grad_group_capacity(int* max_members, int* max_
 extern "C" size_t dro_conv2d_weight_grad_group_workspace_bytes(const dro_wgrad_member* members, int nmember,
                                                               int KH, int KW) {
   WgGroupPlan pl;
-  return group_setup(members, nmember, KH, KW, 0, &pl, nullptr) == DRO_OK ? pl.bytes : 0;
+  return group_setup(members, nullptr, nmember, KH, KW, 0, &pl, nullptr) == DRO_OK ? pl.bytes : 0;
 }
 
 extern "C" int dro_conv2d_weight_grad_group(const dro_wgrad_member* members, int nmember, int KH, int KW,
                                             int act, void* workspace, size_t workspace_bytes, void* stream) {
+  return dro_conv2d_weight_grad_group_ex(members, nullptr, nmember, KH, KW, act, workspace, workspace_bytes,
+                                         stream);
+}
+
+extern "C" int dro_conv2d_weight_grad_group_ex(const dro_wgrad_member* members, const dro_wgrad_gap* gaps,
+                                               int nmember, int KH, int KW, int act, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
   WgGroup g = {};
   WgGroupPlan pl;
   int st;
-  if ((st = group_setup(members, nmember, KH, KW, act, &pl, &g))) return st;
+  if ((st = group_setup(members, gaps, nmember, KH, KW, act, &pl, &g))) return st;
   if ((st = check_ws(workspace, workspace_bytes, pl.bytes, "conv2d_weight_grad_group"))) return st;
   char* ws = static_cast<char*>(workspace);
   const int T = KH * KW;
@@ -3797,4 +3890,92 @@ extern "C" int dro_gru_backward_elem(int stage, int B, int hd, int H, int W, con
   hipLaunchKernelGGL(gru_elem_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0,
                      (hipStream_t)stream, stage, hd, H * W, dhn, zr, q, h, drh, dq, dzr, dh);
   return launch_status("gru_elem_kernel launch failed");
+}
+
+// ------------------------------------------------------------------ n-way sum
+// out = ((g0 + g1) + g2) + ... over up to kSumMax dense tensors, two
+// independent sets per launch (the summed pre-activation gradients of a GRU
+// half's gate and candidate convs, whose context share is back-propagated
+// once: hip/conv.py CtxHoist).  float4 items where every pointer of the set is
+// 16-byte aligned, the rest one element per thread.
+namespace dro {
+constexpr int kSumMax = 8;
+struct SumN {
+  const float* src[2][kSumMax];
+  float* out[2];
+  long long n[2], nvec[2];   // elements; float4 items of them
+  int cnt[2];
+};
+
+template <int S>
+__device__ __forceinline__ void sum_n_item(const SumN& a, long long i) {
+  if (i < a.nvec[S]) {
+    float4 v = reinterpret_cast<const float4*>(a.src[S][0])[i];
+#pragma unroll
+    for (int k = 1; k < kSumMax; ++k) {
+      if (k < a.cnt[S]) {
+        const float4 w = reinterpret_cast<const float4*>(a.src[S][k])[i];
+        v.x += w.x;
+        v.y += w.y;
+        v.z += w.z;
+        v.w += w.w;
+      }
+    }
+    reinterpret_cast<float4*>(a.out[S])[i] = v;
+  } else {
+    const long long j = 4 * a.nvec[S] + (i - a.nvec[S]);
+    float v = a.src[S][0][j];
+#pragma unroll
+    for (int k = 1; k < kSumMax; ++k) {
+      if (k < a.cnt[S]) v += a.src[S][k][j];
+    }
+    a.out[S][j] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void sum_n_kernel(SumN a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long items0 = a.n[0] - 3 * a.nvec[0], items1 = a.n[1] - 3 * a.nvec[1];
+  if (i < items0) sum_n_item<0>(a, i);
+  else if (i - items0 < items1) sum_n_item<1>(a, i - items0);
+}
+}  // namespace dro
+
+extern "C" int dro_sum_n(const float* const* srcs_a, int na, float* out_a, long long numel_a,
+                         const float* const* srcs_b, int nb, float* out_b, long long numel_b, void* stream) {
+  if (na < 1 || na > kSumMax || nb < 0 || nb > kSumMax || numel_a < 1 || (nb > 0 && numel_b < 1)) {
+    set_error("sum_n: 1..8 tensors of at least one element per set");
+    return DRO_E_SHAPE;
+  }
+  if (!srcs_a || !out_a || (nb > 0 && (!srcs_b || !out_b))) {
+    set_error("sum_n: NULL pointer");
+    return DRO_E_NULL;
+  }
+  SumN a = {};
+  long long items = 0;
+  for (int s = 0; s < 2; ++s) {
+    const float* const* srcs = s == 0 ? srcs_a : srcs_b;
+    const int cnt = s == 0 ? na : nb;
+    a.cnt[s] = cnt;
+    a.out[s] = s == 0 ? out_a : out_b;
+    a.n[s] = cnt ? (s == 0 ? numel_a : numel_b) : 0;
+    bool al = (reinterpret_cast<uintptr_t>(a.out[s]) & 15) == 0;
+    for (int k = 0; k < cnt; ++k) {
+      if (!srcs[k]) {
+        set_error("sum_n: NULL pointer");
+        return DRO_E_NULL;
+      }
+      a.src[s][k] = srcs[k];
+      al = al && (reinterpret_cast<uintptr_t>(srcs[k]) & 15) == 0;
+    }
+    a.nvec[s] = al ? a.n[s] / 4 : 0;
+    items += a.n[s] - 3 * a.nvec[s];
+  }
+  const long long blocks = (items + 255) / 256;
+  if (blocks >= (1LL << 31)) {
+    set_error("sum_n: sizes out of range");
+    return DRO_E_SHAPE;
+  }
+  hipLaunchKernelGGL(sum_n_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  return launch_status("sum_n_kernel launch failed");
 }

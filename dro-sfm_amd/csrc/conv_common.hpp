@@ -106,6 +106,11 @@ struct IgArgs {
   Slice src[kMaxSrc];     // forward inputs (virtual concat); read by index from the kernarg segment
   int cbase[kMaxSrc];     // first virtual channel of each source (Cin for unused)
   const float* weight;    // [Cout][Cin][KH][KW]
+  // halo data gradient (dconv_kernel MODE 1) over a column range of a wider
+  // weight [Cout][wcin][KH][KW]: GEMM row r reads weight column
+  // r + (r >= wgap_at ? wgap_len : 0); wgap_at is a multiple of the row tile.
+  // wcin = Cin, wgap_len = 0: the weight as it is (launch_igemm's default)
+  int wcin, wgap_at, wgap_len;
   const float* bias;      // [Cout] or nullptr
   float alpha;            // output scale (act none only)
   float* out;             // forward output slice base

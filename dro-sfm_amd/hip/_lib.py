@@ -100,11 +100,15 @@ def load():
     _sig(lib.dro_convgru_gates_forward, P, I, P, P, I, I, I, I, I, I, P, P, P, P, Z, S)
     _sig(lib.dro_convgru_blend_forward, P, I, P, P, I, I, I, I, I, I, P, P, P, P, I, I, P, P, Z, S)
     _sig(lib.dro_conv2d_backward, P, I, P, I, I, I, I, I, I, I, F, P, P, P, P, P, P, P, P, I, P, P, Z, S)
+    _sig(lib.dro_conv2d_backward_gapped, P, I, P, I, I, I, I, I, I, I, I, I, P, P, P, P, P, P, Z, S)
+    _sig(lib.dro_sum_n, P, I, P, LL, P, I, P, LL, S)
     _sig(lib.dro_conv2d_weight_grad_multi_workspace_bytes, I, I, I, I, I, I, I, I, restype=Z)
     _sig(lib.dro_conv2d_weight_grad_multi, P, I, I, I, I, I, I, I, I, I, F, P, P, I, P, Z, S)
     _sig(lib.dro_conv2d_weight_grad_group_capacity, P, P)
     _sig(lib.dro_conv2d_weight_grad_group_workspace_bytes, P, I, I, I, restype=Z)
     _sig(lib.dro_conv2d_weight_grad_group, P, I, I, I, I, P, Z, S)
+    _sig(lib.dro_conv2d_weight_grad_multi_ex, P, I, I, I, I, I, I, I, I, I, F, P, P, I, P, P, Z, S)
+    _sig(lib.dro_conv2d_weight_grad_group_ex, P, P, I, I, I, I, P, Z, S)
     _sig(lib.dro_adam_step, P, P, P, P, ctypes.c_longlong, P, P, S)
     _sig(lib.dro_gru_backward_elem, I, I, I, I, I, P, P, P, P, P, P, P, P, S)
     _sig(lib.dro_convgru_candidate_backward, P, I, P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, Z, S)
@@ -141,10 +145,10 @@ EXPORTED = (
     "dro_batchnorm_workspace_bytes", "dro_batchnorm_relu_forward", "dro_batchnorm_relu_backward",
     "dro_weight_split_bytes", "dro_weight_split",
     "dro_conv2d_workspace_bytes", "dro_conv2d_plan", "dro_conv2d_plan_cin", "dro_conv2d_strided_plan", "dro_debug_conv_stamps", "dro_conv_log", "dro_conv_log_read", "dro_conv2d_forward", "dro_convgru_gates_forward",
-    "dro_convgru_blend_forward", "dro_conv2d_backward",
+    "dro_convgru_blend_forward", "dro_conv2d_backward", "dro_conv2d_backward_gapped", "dro_sum_n",
     "dro_conv2d_weight_grad_multi_workspace_bytes", "dro_conv2d_weight_grad_multi",
     "dro_conv2d_weight_grad_group_capacity", "dro_conv2d_weight_grad_group_workspace_bytes",
-    "dro_conv2d_weight_grad_group",
+    "dro_conv2d_weight_grad_group", "dro_conv2d_weight_grad_multi_ex", "dro_conv2d_weight_grad_group_ex",
     "dro_gru_backward_elem", "dro_convgru_candidate_backward", "dro_convgru_gates_backward", "dro_adam_step",
     "dro_bn_state_bytes", "dro_bn_apply", "dro_bn_backward_apply", "dro_conv2d_bn_forward", "dro_conv2d_bn_backward_data",
 )

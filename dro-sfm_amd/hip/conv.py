@@ -48,6 +48,15 @@ Their queued output gradients stay alive until the flush (about 100 MB at
 the KITTI metric shape).  Weights queued from several streams, with more
 than 16 uses, or of the 7x7 shapes keep the per-weight launch.
 
+Context hoist (direct path, default on, set_context_hoist / DRO_CTX_HOIST=0):
+the context source of an update block is the same tensor in every GRU
+application, so its share of the GRU convs' backward is taken once per
+(block, half) from the summed pre-activation gradients instead of in every
+application: the data-gradient kernels drop the context's row tiles, the
+queued weight gradients run without the context channels, and one sum launch,
+two data gradients and two single-use weight-gradient members per half supply
+the context's gradient and the weights' context columns (CtxHoist).
+
 Split-bf16 engine (set_split_engine, default off): the 1x5 / 5x1 / 3x3 / 1x1
 forward and data-gradient GEMMs run on bf16 MFMA over operands split into three
 bf16 terms (csrc/xconv.hip, f32 accuracy at 2.67x the f32 MFMA rate).  Each
@@ -285,19 +294,26 @@ def set_batched_weight_grads(enabled):
     _BATCH[0] = bool(enabled)
 
 
-def _queue_weight_grad(srcs, wshape, act, alpha, dout, y, gw, gb, weight=None):
+class DroWgradGap(ctypes.Structure):
+    _fields_ = [("wcin", ctypes.c_int), ("gap_at", ctypes.c_int), ("gap_len", ctypes.c_int)]
+
+
+def _queue_weight_grad(srcs, wshape, act, alpha, dout, y, gw, gb, weight=None, gap=None):
     """Queue one use's weight(+bias) gradient for the end-of-backward batch;
-    False when this conv shape is not batched (the caller launches it)."""
+    False when this conv shape is not batched (the caller launches it).
+    gap = (wcin, gap_at, gap_len): the sources (wshape[1] channels) are the
+    columns of the [Cout, wcin, KH, KW] gradient `gw` but [gap_at, +gap_len)."""
     Cout, Cin, KH, KW = wshape
     if not _BATCH[0] or not ((KH, KW) in _MULTI_SHAPES or ((KH, KW) in _CAT_SHAPES and len(srcs) == 1)):
         return False
     B, _, H, W = srcs[0].shape
     key = (gw.data_ptr(), gb.data_ptr() if gb is not None else 0, B, H, W, act, float(alpha),
-           tuple(t.shape[1] for t in srcs))
+           tuple(t.shape[1] for t in srcs), gap)
     ent = _PENDING.get(key)
     cur = torch.cuda.current_stream()
     if ent is None:
-        ent = _PENDING[key] = ((B, H, W, Cin, Cout, KH, KW, act, float(alpha), gw, gb, len(srcs), weight), [], [])
+        meta = (B, H, W, Cin, Cout, KH, KW, act, float(alpha), gw, gb, len(srcs), weight)
+        ent = _PENDING[key] = (meta if gap is None else (*meta, gap), [], [])
     ent[1].append((list(srcs), dout, y))
     if all(s != cur for s in ent[2]):
         ent[2].append(cur)
@@ -306,6 +322,18 @@ def _queue_weight_grad(srcs, wshape, act, alpha, dout, y, gw, gb, weight=None):
         stream = torch.cuda.current_stream()
         torch.autograd.Variable._execution_engine.queue_callback(lambda: flush_weight_grads(stream))
     return True
+
+
+def _gap_of(meta):
+    """The item's weight column gap (a 14th entry of its meta tuple), or None."""
+    return meta[13] if len(meta) > 13 else None
+
+
+def _same_target(m0, m1):
+    """Two items write the same gradient elements: the same tensor, unless
+    both write column ranges of it that differ (a hoisted weight's two members)."""
+    g0, g1 = _gap_of(m0), _gap_of(m1)
+    return m0[9].data_ptr() == m1[9].data_ptr() and (g0 is None or g1 is None or g0 == g1)
 
 
 def _covers(t, ptr_):
@@ -352,13 +380,13 @@ def _groupable(item):
 
 def _ready(item):
     """A complete item joins its stream's group; a group that cannot take it
-    (capacity, or a member that writes the same gradient) is launched first."""
+    (capacity, or a member that writes the same gradient columns) is launched first."""
     meta, uses, streams = item
     key = (streams[0], meta[5], meta[6], meta[7])
     group = _READY.setdefault(key, [])
     max_members, max_uses = _group_capacity()
     if (len(group) + 1 > max_members or sum(len(it[1]) for it in group) + len(uses) > max_uses
-            or any(it[0][9].data_ptr() == meta[9].data_ptr() for it in group)):
+            or any(_same_target(it[0], meta) for it in group)):
         _launch_group(key, _READY.pop(key))
         group = _READY.setdefault(key, [])
     group.append(item)
@@ -380,6 +408,8 @@ def flush_param_grads(param):
     if g is None or not _PENDING:
         return None
     p0 = g.data_ptr()
+    for h in list(_HOISTS):
+        h.param_ready(p0)      # the context columns of this gradient are queued with the rest
     keys = [k for k, (meta, _, _) in _PENDING.items() if _covers(meta[9], p0) or _covers(meta[10], p0)]
     if not keys:
         return None
@@ -413,6 +443,9 @@ def flush_weight_grads(stream=None):
     waits for the other streams' groups), or one launch + one reduction per
     weight per 16 uses on `stream`."""
     _PENDING_CB[0] = False
+    for h in _HOISTS:      # (every sink node has run by now: only a broken backward leaves one)
+        h.spent, h.halves = True, {}
+    del _HOISTS[:]
     items = list(_PENDING.values())
     _PENDING.clear()
     single = [it for it in items if not _groupable(it)]
@@ -435,8 +468,12 @@ def _launch_group(key, group):
     stream, KH, KW, act = key
     n = len(group)
     keep, members = [], (DroWgradMember * n)()
+    gaps = (DroWgradGap * n)() if any(_gap_of(it[0]) is not None for it in group) else None
     for i, (meta, uses, _) in enumerate(group):
-        B, H, W, Cin, Cout, _, _, _, alpha, gw, gb, nsrc, _ = meta
+        B, H, W, Cin, Cout, _, _, _, alpha, gw, gb, nsrc, _ = meta[:13]
+        gap = _gap_of(meta)
+        if gaps is not None:
+            gaps[i].wcin, gaps[i].gap_at, gaps[i].gap_len = gap if gap is not None else (Cin, 0, 0)
         sl = [_slices(srcs) for srcs, _, _ in uses]
         arr = (DroWgradUse * len(uses))()
         for j, (_, dout, y) in enumerate(uses):
@@ -453,8 +490,8 @@ def _launch_group(key, group):
     with torch.cuda.stream(stream):
         nb = int(lib.dro_conv2d_weight_grad_group_workspace_bytes(members, n, KH, KW))
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=group[0][0][9].device)
-        check(lib.dro_conv2d_weight_grad_group(members, n, KH, KW, act, ptr(ws), nb,
-                                               ctypes.c_void_p(stream.cuda_stream)),
+        check(lib.dro_conv2d_weight_grad_group_ex(members, gaps, n, KH, KW, act, ptr(ws), nb,
+                                                  ctypes.c_void_p(stream.cuda_stream)),
               "dro_conv2d_weight_grad_group")
 
 
@@ -473,7 +510,9 @@ def _launch_weight_grads(items, stream):
                         x.record_stream(stream)
     with torch.cuda.stream(stream):
         for meta, uses, _ in items:
-            B, H, W, Cin, Cout, KH, KW, act, alpha, gw, gb, nsrc, weight = meta
+            B, H, W, Cin, Cout, KH, KW, act, alpha, gw, gb, nsrc, weight = meta[:13]
+            gap = _gap_of(meta)
+            cgap = ctypes.byref(DroWgradGap(*gap)) if gap is not None else None
             if (KH, KW) in _CAT_SHAPES:
                 # every use on the batch axis (broadcast sources materialise),
                 # one weight-gradient launch + one split sum for all of them
@@ -493,9 +532,9 @@ def _launch_weight_grads(items, stream):
                     arr[i].y = y.data_ptr() if y is not None else None
                 nb = int(lib.dro_conv2d_weight_grad_multi_workspace_bytes(n, B, H, W, Cin, Cout, KH, KW))
                 ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=gw.device)
-                check(lib.dro_conv2d_weight_grad_multi(arr, n, nsrc, B, H, W, Cout, KH, KW, act,
-                                                       ctypes.c_float(alpha), ptr(gw), ptr(gb), 1,
-                                                       ptr(ws), nb, stream_of(gw)),
+                check(lib.dro_conv2d_weight_grad_multi_ex(arr, n, nsrc, B, H, W, Cout, KH, KW, act,
+                                                          ctypes.c_float(alpha), ptr(gw), ptr(gb), 1, cgap,
+                                                          ptr(ws), nb, stream_of(gw)),
                       "dro_conv2d_weight_grad_multi")
     return stream
 
@@ -876,6 +915,187 @@ class GruChain:
 
 
 _SEPGRU_CHAIN = []   # the GruChain of the call being set up (sepconvgru_half)
+_SEPGRU_CTX = []     # the index in xs of the recurrence's constant context source, same call
+
+# Context hoist (direct path; DRO_CTX_HOIST=0 switches it off for A/B runs):
+# the context source of an update block is the same tensor in every GRU
+# application, so its data gradient sum_t conv^T(G_t, W[:, ctx]) is
+# conv^T(sum_t G_t, W[:, ctx]) -- one data gradient per gate / candidate conv
+# and GRU half instead of one per application.
+_CTX_HOIST = [os.environ.get("DRO_CTX_HOIST", "1") != "0"]
+_SUM_MAX = 8         # tensors per set of one dro_sum_n launch
+_HOIST_PLANS = {}
+
+
+def set_context_hoist(enabled):
+    """Back-propagate the context share of the SepConvGRU convs once per
+    (block, half) from the summed output gradients (True, default) or in every
+    application's data gradient (False)."""
+    _CTX_HOIST[0] = bool(enabled)
+
+
+def _plan(rows, kch, KH, KW, B, H, W, cin):
+    """(halo, row tile) of the data-gradient / forward plan (csrc/conv.hip plan_igemm)."""
+    key = (rows, kch, KH, KW, B, H, W, cin)
+    v = _HOIST_PLANS.get(key)
+    if v is None:
+        info = (ctypes.c_longlong * 16)()
+        check(_lib.load().dro_conv2d_plan_cin(rows, kch, KH, KW, B, H, W, cin, info), "dro_conv2d_plan_cin")
+        v = _HOIST_PLANS[key] = (int(info[0]), int(info[1]))
+    return v
+
+
+def _hoistable(B, H, W, hd, cd, wcin, KH, KW):
+    """The per-application data gradients (rows = wcin) drop the context's row
+    tiles only when [hd, hd + cd) is tile aligned on the halo kernel, and the
+    hoisted ones (rows = cd) need the halo kernel and float4-aligned columns."""
+    T = KH * KW
+    if (wcin * T) % 4 or (hd * T) % 4:
+        return False
+    for cout in (2 * hd, hd):
+        halo, bm = _plan(wcin, cout, KH, KW, B, H, W, wcin)
+        if not halo or hd % bm or cd % bm:
+            return False
+        if not _plan(cd, cout, KH, KW, B, H, W, wcin)[0]:
+            return False
+    return True
+
+
+def sum_n(ts, out=None, ts2=None, out2=None):
+    """out = ((ts[0] + ts[1]) + ts[2]) + ... (1..8 dense fp32 tensors of one
+    size), and likewise out2 from ts2 in the same launch (csrc/conv.hip dro_sum_n)."""
+    lib = _lib.load()
+    require_device(*ts, *(ts2 or ()), what="sum_n")
+    for t in (*ts, *(ts2 or ())):
+        if not t.is_contiguous():
+            raise RuntimeError("sum_n: tensors must be contiguous")
+    out = torch.empty_like(ts[0]) if out is None else out
+    pa = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    pb, nb, n2 = None, 0, 0
+    if ts2:
+        out2 = torch.empty_like(ts2[0]) if out2 is None else out2
+        pb, nb, n2 = (ctypes.c_void_p * len(ts2))(*[t.data_ptr() for t in ts2]), len(ts2), ts2[0].numel()
+    check(lib.dro_sum_n(pa, len(ts), ptr(out), ts[0].numel(), pb, nb, ptr(out2) if ts2 else None, n2,
+                        stream_of(out)), "dro_sum_n")
+    return (out, out2) if ts2 else out
+
+
+def conv2d_backward_gapped(grad_out, weight, gap_at, gap_len, targets, accumulate):
+    """conv^T(grad_out, W[:, columns]) for sources that cover the weight's input
+    columns but [gap_at, gap_at + gap_len): source i's gradient into the dense
+    targets[i] (added when accumulate[i]).  csrc/conv.hip dro_conv2d_backward_gapped."""
+    lib = _lib.load()
+    Cout, wcin, KH, KW = weight.shape
+    B, _, H, W = grad_out.shape
+    n = len(targets)
+    cin = sum(t.shape[1] for t in targets)
+    sl = (DroSlice * n)(*[DroSlice(t.data_ptr(), t.shape[1], t.shape[1], 0, 0) for t in targets])
+    ws, nws = _workspace(B, H, W, cin, Cout, KH, KW, grad_out.device)
+    ptrs, ctot, coff = _grad_targets(list(targets))
+    acc = (ctypes.c_int * n)(*[int(a) for a in accumulate])
+    check(lib.dro_conv2d_backward_gapped(sl, n, ptr(weight), wcin, gap_at, gap_len, B, H, W, Cout, KH, KW,
+                                         ptr(grad_out), ptrs, ctot, coff, acc, ptr(ws), nws,
+                                         stream_of(grad_out)), "dro_conv2d_backward_gapped")
+
+
+class _HoistHalf:
+    """One GRU half's share of a CtxHoist: the gate (0) and candidate (1) convs'
+    weights and flat gradient views, the context source, the stream its
+    backward runs on, the registered pre-activation gradients and their sums."""
+    __slots__ = ("w", "gw", "hd", "ctx", "stream", "g", "sums")
+
+    def __init__(self, w, gw, hd, ctx):
+        self.w, self.gw, self.hd, self.ctx = w, gw, hd, ctx
+        self.stream = torch.cuda.current_stream()
+        self.g = ([], [])
+        self.sums = None
+
+
+_HOISTS = []     # CtxHoists with registered halves that have not been flushed yet
+
+
+class CtxHoist:
+    """The hoisted context share of one update block's GRU backward, owned by
+    the context source's gradient sink (hip.ops.GradSinkState.hoist).  Every GRU
+    half's backward leaves the context out of its data gradients (no target:
+    the kernels drop its row tiles) and of its queued weight gradients (the
+    sources without it, a column gap in the target), and registers its
+    pre-activation gradients dzr_t, dq_t here.  Per half, ONE dro_sum_n launch
+    forms sum_t dzr_t and sum_t dq_t and queues the context columns' weight
+    gradients -- one use each, sources = [context] -- beside the half's
+    multi-use ones: from flush_param_grads when the trainer's gradient buckets
+    report one of the half's parameters complete (autograd runs a parameter's
+    hook after its last use, so every dzr_t / dq_t is registered by then, and
+    the bucket cannot go out without the context columns), else when the sink
+    is handed on.  The sink's backward node -- autograd runs it after every
+    consumer -- calls flush(sink): the two data gradients of the sums through
+    each half's context columns go into the sink's buffer.  One shot: a second
+    backward through the same graph (retain_graph) runs unhoisted."""
+    __slots__ = ("halves", "spent")
+    stats = {"hoisted": 0, "flushes": 0, "sums": 0}    # (tests)
+
+    def __init__(self):
+        self.halves = {}     # (gate weight, candidate weight) -> _HoistHalf
+        self.spent = False
+
+    def add(self, w, gw, hd, ctx, dzr, dq):
+        key = (w[0].data_ptr(), w[1].data_ptr())
+        ent = self.halves.get(key)
+        if ent is None:
+            ent = self.halves[key] = _HoistHalf(w, gw, hd, ctx.detach())
+            if self not in _HOISTS:
+                _HOISTS.append(self)
+        ent.g[0].append(dzr)
+        ent.g[1].append(dq)
+        CtxHoist.stats["hoisted"] += 1
+
+    @staticmethod
+    def _sums(gz, gq):
+        """The two sets' fixed-order sums, _SUM_MAX tensors per launch."""
+        sz = sq = None
+        while gz or gq:
+            cz, gz = gz[:_SUM_MAX], gz[_SUM_MAX:]
+            cq, gq = gq[:_SUM_MAX], gq[_SUM_MAX:]
+            if len(cz) == 1 and len(cq) == 1 and sz is None:
+                return cz[0], cq[0]
+            sz, sq = sum_n(cz, sz, cq, sq)
+            CtxHoist.stats["sums"] += 1
+            if gz:       # later chunks continue the chain from the running sums
+                gz, gq = [sz, *gz], [sq, *gq]
+        return sz, sq
+
+    def _prepare(self, ent):
+        """Sum the half's gradients and queue its context-column weight gradients (once)."""
+        if ent.sums is not None:
+            return
+        with torch.cuda.stream(ent.stream):
+            ent.sums = self._sums(list(ent.g[0]), list(ent.g[1]))
+            cd = ent.ctx.shape[1]
+            for s, w, gw in zip(ent.sums, ent.w, ent.gw):
+                Cout, wcin, KH, KW = w.shape
+                if not _queue_weight_grad([ent.ctx], (Cout, cd, KH, KW), 0, 1.0, s, None, gw, None,
+                                          gap=(wcin, 0, ent.hd)):
+                    raise RuntimeError("context hoist: the context columns' weight gradient was not queued")
+
+    def param_ready(self, p0):
+        """A parameter whose gradient starts at address p0 is complete."""
+        for ent in self.halves.values():
+            if any(_covers(gw, p0) for gw in ent.gw):
+                self._prepare(ent)
+
+    def flush(self, sink):
+        if self in _HOISTS:
+            _HOISTS.remove(self)
+        if self.spent or not self.halves:
+            return
+        self.spent = True
+        halves, self.halves = self.halves, {}
+        for ent in halves.values():
+            self._prepare(ent)
+            for s, w in zip(ent.sums, ent.w):
+                buf, acc = sink.target()
+                conv2d_backward_gapped(s, w, 0, ent.hd, [buf], [acc])
+        CtxHoist.stats["flushes"] += 1
 
 
 # ------------------------------------------------------------------ dro::sepconvgru_half
@@ -942,6 +1162,18 @@ def _sepgru_setup(ctx, inputs, output):
     ctx.scope = current_scope()
     ctx.keys = (("zr", wz.data_ptr(), wr.data_ptr()), ("q", wq.data_ptr()))
     ctx.direct = _SEPGRU_DIRECT.pop() if _SEPGRU_DIRECT else None
+    # the constant context source (xs[0]) with a gradient sink: its share of
+    # this half's data gradients is hoisted to the sink's flush (CtxHoist)
+    ci = _SEPGRU_CTX.pop() if _SEPGRU_CTX else None
+    ctx.hoist = None
+    if (ci == 0 and _CTX_HOIST[0] and ctx.direct is not None and ctx.sinks[0] is not None
+            and ctx.wsplit == (None, None)
+            and _hoistable(h.shape[0], h.shape[2], h.shape[3], h.shape[1], xs[0].shape[1], wq.shape[1],
+                           wq.shape[2], wq.shape[3])):
+        st = ctx.sinks[0]
+        if st.hoist is None:
+            st.hoist = CtxHoist()
+        ctx.hoist = st.hoist
     chain = _SEPGRU_CHAIN.pop() if _SEPGRU_CHAIN else None
     ctx.chain_first = ctx.chain_prev = None
     if chain is not None and _GRU_CHAIN:
@@ -991,7 +1223,11 @@ def _sepgru_backward(ctx, dhn, _gzr, _grh, _gq):
     sinks = ctx.sinks
     dxs = [torch.empty(B, x.shape[1], H, W, device=h.device) if need_x[i] and sinks[i] is None
            else None for i, x in enumerate(xs)]
-    sk = [sn.target() if sn is not None else (None, 0) for sn in sinks]
+    # hoisted context (xs[0]): no target here -- the data-gradient kernels drop
+    # its row tiles -- and its sink is not marked written by this half
+    hoist = ctx.hoist if ctx.hoist is not None and not ctx.hoist.spent and _BATCH[0] else None
+    sk = [sn.target() if sn is not None and not (hoist is not None and i == 0) else (None, 0)
+          for i, sn in enumerate(sinks)]
     tg = [t if sn is not None else d for (t, _), sn, d in zip(sk, sinks, dxs)]
     qacc0 = [0] + [a for _, a in sk]
     zb, qb = ctx.wsplit
@@ -1004,7 +1240,16 @@ def _sepgru_backward(ctx, dhn, _gzr, _grh, _gq):
                                                      [_placeholder(t, h.device) for t in [None, *tg]], qacc0)
         else:
             _conv_bwd([rh, *xs], wq, None, dq, 0, 1.0, [drh, *tg], qacc0, wsplit=qb)
-        if not _queue_weight_grad([rh, *xs], wq.shape, 0, 1.0, dq, None, gwq, gbq):
+        # hoisted: the queued weight gradients run over the sources without the
+        # context and leave its columns of the gradient to the hoist's member
+        xw = xs[1:] if hoist is not None else xs
+        gap = (wq.shape[1], hd, xs[0].shape[1]) if hoist is not None else None
+        wcin = wq.shape[1] - (gap[2] if gap else 0)
+        if _queue_weight_grad([rh, *xw], (hd, wcin, *wq.shape[2:]), 0, 1.0, dq, None, gwq, gbq, gap=gap):
+            pass
+        elif hoist is not None:
+            raise RuntimeError("sepconvgru_half: hoisted context with unbatched weight gradients")
+        else:
             _conv_bwd([rh, *xs], wq, None, dq, 0, 1.0, [None] * (1 + len(xs)), [0] * (1 + len(xs)), gwq, gbq, 1)
         if not (_GRU_FOLD and qb is None):
             torch.ops.dro.gru_backward_elem(2, None, zr, None, h, drh, None, dzr, dh)
@@ -1029,8 +1274,15 @@ def _sepgru_backward(ctx, dhn, _gzr, _grh, _gq):
             GruChain.folded += 1
         else:
             _conv_bwd([h, *xs], wzr, None, dzr, 0, 1.0, [dh, *tg], [1] * (1 + len(xs)), wsplit=zb)
-        if not _queue_weight_grad([h, *xs], wzr.shape, 0, 1.0, dzr, None, gwzr, gbzr):
+        if _queue_weight_grad([h, *xw], (2 * hd, wcin, *wzr.shape[2:]), 0, 1.0, dzr, None, gwzr, gbzr, gap=gap):
+            pass
+        elif hoist is not None:
+            raise RuntimeError("sepconvgru_half: hoisted context with unbatched weight gradients")
+        else:
             _conv_bwd([h, *xs], wzr, None, dzr, 0, 1.0, [None] * (1 + len(xs)), [0] * (1 + len(xs)), gwzr, gbzr, 1)
+        if hoist is not None:
+            # dzr and dq are complete in stream order; summed once per half
+            hoist.add((wzr, wq), (gwzr, gwq), hd, xs[0], dzr, dq)
         return (dh if need_h and not h_in_sink else None, *nones, dxs, None, None)
     gwq, gbq, qacc, qfirst = _grad_buffers(ctx.scope, ctx.keys[1], wq, hd, h.device)
     _conv_bwd([rh, *xs], wq, None, dq, 0, 1.0, [drh, *tg], qacc0, gwq, gbq, qacc, qb)
@@ -1047,8 +1299,11 @@ def _sepgru_backward(ctx, dhn, _gzr, _grh, _gq):
 torch.library.register_autograd("dro::sepconvgru_half", _sepgru_backward, setup_context=_sepgru_setup)
 
 
-def sepconvgru_half(h, convz, convr, convq, xs, chain=None):
+def sepconvgru_half(h, convz, convr, convq, xs, chain=None, context=None):
     """h' for one SepConvGRU direction; xs: the input sources (virtual concat).
+    context: the index in xs of a source that is the same tensor in every
+    application of a recurrence (the update blocks' context features, xs[0]):
+    its gradient share is then back-propagated once (CtxHoist).
     chain: one GruChain shared by the two halves of one SepConvGRU (the
     second half's backward then runs the first half's stage 1).
     torch.ops.dro.sepconvgru_half."""
@@ -1073,9 +1328,11 @@ def sepconvgru_half(h, convz, convr, convq, xs, chain=None):
         wzr, bzr = ent
     _SEPGRU_DIRECT[:] = [direct] if direct is not None else []
     _SEPGRU_CHAIN[:] = [chain] if chain is not None else []
+    _SEPGRU_CTX[:] = [context] if context is not None else []
     try:
         return torch.ops.dro.sepconvgru_half(h, convz.weight, convz.bias, convr.weight, convr.bias, convq.weight,
                                              convq.bias, list(xs), wzr, bzr)[0]
     finally:
         _SEPGRU_DIRECT.clear()
         _SEPGRU_CHAIN.clear()
+        _SEPGRU_CTX.clear()

@@ -42,9 +42,10 @@ def _disp_range(min_depth, max_depth):
 class GradSinkState:
     """A sink's dense gradient buffer and whether a consumer has written it yet
     (the first consumer to run overwrites, the later ones add: no zero-fill)."""
-    __slots__ = ("buf", "written")
+    __slots__ = ("buf", "written", "hoist")
 
     def __init__(self, like):
+        self.hoist = None   # hip.conv.CtxHoist: gradient shares launched once, when the sink is handed on
         # channels-last reference maps keep their layout (the cost kernels
         # scatter into it); everything else gets a dense NCHW buffer
         self.buf = (torch.empty_like(like) if _is_channels_last_refs(like)
@@ -79,6 +80,8 @@ class _GradSink(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         st = ctx.state
+        if st.hoist is not None:
+            st.hoist.flush(st)    # every consumer has run: the hoisted shares go into the buffer now
         if not st.written:
             return g, None
         st.written = False

@@ -135,10 +135,10 @@ class SepConvGRU(nn.Module):
         for axis, k, pad in (("1", (1, 5), (0, 2)), ("2", (5, 1), (2, 0))):
             declare(self, {g + axis: (cin, hidden_dim, k, pad) for g in ("convz", "convr", "convq")})
 
-    def _gate(self, h, xs, axis, chain=None):
+    def _gate(self, h, xs, axis, chain=None, context=None):
         cz, cr, cq = (getattr(self, g + axis) for g in ("convz", "convr", "convq"))
         if _BACKEND == "hip":
-            return hip.sepconvgru_half(h, cz, cr, cq, xs, chain=chain)
+            return hip.sepconvgru_half(h, cz, cr, cq, xs, chain=chain, context=context)
         z, r = conv_cat([h, *xs], (cz, cr), "sigmoid")
         q = conv([r * h, *xs], cq.weight, cq.bias, "tanh")
         return (1 - z) * h + z * q
@@ -147,13 +147,15 @@ class SepConvGRU(nn.Module):
         """z|r gates of each direction are one fused conv (trainer layout hint)."""
         return fused_groups(self.convz1, self.convr1) + fused_groups(self.convz2, self.convr2)
 
-    def forward(self, h, x):
-        """x: the input tensor, or a list of tensors read as their channel concat."""
+    def forward(self, h, x, context=None):
+        """x: the input tensor, or a list of tensors read as their channel concat.
+        context: the index in that list of a source that is the same tensor in
+        every application of the recurrence (hip.conv.CtxHoist)."""
         xs = _as_list(x)
         # the two halves' backward kernels are linked (hip.conv.GruChain): the
         # middle state is read by the second half only
         chain = hip_conv.GruChain() if _BACKEND == "hip" else None
-        return self._gate(self._gate(h, xs, "1", chain), xs, "2", chain)
+        return self._gate(self._gate(h, xs, "1", chain, context), xs, "2", chain, context)
 
 
 class _Projection(nn.Module):
@@ -247,7 +249,7 @@ class BasicUpdateBlockDepth(nn.Module):
             inv_depth = hip.grad_sink(inv_depth)
             feat = self.encoder.sources(inv_depth, cost_func(scale_func(inv_depth)[0]))
             # the state feeds the heads and the next GRU step: one gradient buffer
-            net = hip.grad_sink(self.depth_gru(net, [context, *feat]))
+            net = hip.grad_sink(self.depth_gru(net, [context, *feat], context=0))
             delta, mask = self.heads(net)
             inv_depth = inv_depth + delta
             invs.append(inv_depth)
@@ -267,7 +269,7 @@ class BasicUpdateBlockPose(nn.Module):
     def forward(self, net, cost_func, pose, inp, seq_len=4):
         seq = []
         for _ in range(seq_len):
-            net = hip.grad_sink(self.pose_gru(net, [inp, *self.encoder.sources(pose, cost_func(pose))]))
+            net = hip.grad_sink(self.pose_gru(net, [inp, *self.encoder.sources(pose, cost_func(pose))], context=0))
             pose = self.pose_head(net, pose)               # pose + pose_head(net), one launch
             seq.append(pose)
         return net, seq

@@ -505,6 +505,31 @@ int dro_conv2d_backward(const dro_slice* srcs, int nsrc, const float* weight, in
                         float* grad_bias, int grad_weight_accumulate, const void* wsplit,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* Data gradient of a convolution whose sources cover only some columns of a
+ * wider weight [Cout][wcin][KH][KW]: virtual input channel c (over the
+ * nsrc sources, as in dro_conv2d_backward) reads weight column
+ * c + (c >= gap_at ? gap_len : 0).  With the sources = [context] and
+ * gap_at = 0, gap_len = hd this is conv^T(dout, W[:, hd:hd+cd]): the context
+ * share of a SepConvGRU conv over [h | context | ...], back-propagated once
+ * for the sum of the recurrence's output gradients.  No activation, no weight
+ * gradient; kernel shapes 1x1, 1x5, 5x1, 3x3 with wcin*KH*KW and gap_len*KH*KW
+ * multiples of 4 and gap_at a multiple of the plan's row tile
+ * (dro_conv2d_plan_cin(rows = sum of source channels, kch = Cout, cin = wcin):
+ * info[0] halo must be 1, info[1] the row tile), else DRO_E_SHAPE.  Workspace:
+ * dro_conv2d_workspace_bytes of the virtual Cin. */
+int dro_conv2d_backward_gapped(const dro_slice* srcs, int nsrc, const float* weight, int wcin, int gap_at,
+                               int gap_len, int B, int H, int W, int Cout, int KH, int KW,
+                               const float* dout, float* const* grad_srcs, const int* grad_ctot,
+                               const int* grad_coff, const int* grad_accumulate, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* out = ((g0 + g1) + g2) + ... in that order over n dense fp32 tensors of
+ * numel elements each (1 <= n <= 8), for two independent sets in one launch
+ * (nb = 0: set a only).  srcs_* are host arrays of device pointers, read
+ * before the call returns.  Bitwise equal to the same chain of fp32 adds. */
+int dro_sum_n(const float* const* srcs_a, int na, float* out_a, long long numel_a,
+              const float* const* srcs_b, int nb, float* out_b, long long numel_b, void* stream);
+
 /* Weight (+ bias) gradient of ONE weight over several convolutions that use it
  * (the recurrent update blocks apply each weight once per iteration): one
  * launch (+ one split reduction) for all uses instead of one pair per use.
@@ -585,6 +610,31 @@ size_t dro_conv2d_weight_grad_group_workspace_bytes(const dro_wgrad_member* memb
 
 int dro_conv2d_weight_grad_group(const dro_wgrad_member* members, int nmember, int KH, int KW,
                                  int act, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Weight gradients into a column range of a wider weight: the sources' Cin
+ * virtual channels are the columns of grad_weight [Cout][wcin][KH][KW] but
+ * [gap_at, gap_at + gap_len); channel c is written (or added) to column
+ * c + (c >= gap_at ? gap_len : 0), the other columns are not touched.
+ * 0 <= gap_at <= Cin, Cin + gap_len <= wcin.  The split partials and the
+ * workspace sizes are those of the virtual Cin.  A SepConvGRU weight over
+ * [h | context | features] takes two such gradients: the recurrence's uses
+ * without the context (gap_at = hd, gap_len = cd) and one use of the context
+ * with the summed output gradients (gap_at = 0, gap_len = hd).  The _ex calls
+ * with gap(s) = NULL are the plain calls; gaps[i] belongs to members[i]. */
+typedef struct dro_wgrad_gap {
+  int wcin;     /* the weight's input channels (row length / (KH*KW)) */
+  int gap_at;   /* first virtual channel past the gap */
+  int gap_len;  /* columns left out */
+} dro_wgrad_gap;
+
+int dro_conv2d_weight_grad_multi_ex(const dro_wgrad_use* uses, int nuse, int nsrc, int B, int H, int W,
+                                    int Cout, int KH, int KW, int act, float alpha, float* grad_weight,
+                                    float* grad_bias, int accumulate, const dro_wgrad_gap* gap,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
+int dro_conv2d_weight_grad_group_ex(const dro_wgrad_member* members, const dro_wgrad_gap* gaps, int nmember,
+                                    int KH, int KW, int act, void* workspace, size_t workspace_bytes,
+                                    void* stream);
 
 /* SepConvGRU backward, elementwise parts (update.py:67-70): with zr the saved
  * sigmoid gates [B,2hd,H,W] (z first), q the saved candidate [B,hd,H,W].
