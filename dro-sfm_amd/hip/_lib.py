@@ -78,6 +78,10 @@ def load():
     _sig(lib.dro_depth_metrics_demon_prepare, P, P, P, LL, I, I, I, I, I, F, F, P, P, P, S)
     _sig(lib.dro_depth_metrics_demon_reduce, P, P, P, P, LL, I, I, I, F, F, P, P, S)
     _sig(lib.dro_post_process_inv_depth, P, P, I, I, I, I, P, P, P, S)
+    _sig(lib.dro_depth_clean, P, I, I, I, F, F, I, I, P, S)
+    _sig(lib.dro_depth_fusion, P, P, P, P, P, I, I, I, I, F, F, I, P, P, P, P, S)
+    _sig(lib.dro_backproject_points_workspace_bytes, I, I, I, restype=Z)
+    _sig(lib.dro_backproject_points, P, P, P, P, I, I, I, I, P, P, P, P, S)
     _sig(lib.dro_resize_rgb8_to_tensor, P, I, I, I, I, I, P, P, I, P, P, I, P, P, S)
     _sig(lib.dro_color_jitter_rgb8, P, I, I, I, P, P, S)
     _sig(lib.dro_resize_rgb8, P, I, I, I, I, I, P, P, I, P, P, I, P, P, S)
@@ -138,6 +142,7 @@ EXPORTED = (
     "dro_depth_metrics_blocks", "dro_depth_metrics_workspace_bytes", "dro_depth_metrics_prepare",
     "dro_depth_metrics_reduce", "dro_depth_metrics_median_workspace_bytes", "dro_depth_metrics_median",
     "dro_depth_metrics_demon_prepare", "dro_depth_metrics_demon_reduce", "dro_post_process_inv_depth",
+    "dro_depth_clean", "dro_depth_fusion", "dro_backproject_points_workspace_bytes", "dro_backproject_points",
     "dro_conv2d_strided_workspace_bytes", "dro_conv2d_strided_forward", "dro_conv2d_strided_backward",
     "dro_pose_mean_forward", "dro_pose_mean_backward",
     "dro_resize_rgb8_to_tensor", "dro_color_jitter_rgb8", "dro_resize_rgb8", "dro_rgb8_to_tensor",

@@ -1258,3 +1258,128 @@ def post_process_inv_depth(inv_depth, inv_depth_flipped, method="mean"):
                                          ptr(depth), ptr(depth_pp), stream_of(inv)),
           "dro_post_process_inv_depth")
     return inv_pp, depth, depth_pp
+
+
+# ----------------------------------------------------------------------------
+# sequence reconstruction (csrc/reconstruct.hip)
+# ----------------------------------------------------------------------------
+FUSION_MAX_VIEWS = 8
+FUSION_OUTSIDE = -2          # fuse_depths(record=True): the sample fell outside the source map
+
+
+def _maps(what, *named):
+    """[B,H,W] float32 device maps of one shape, contiguous."""
+    first = named[0][1]
+    if first.dim() != 3:
+        raise RuntimeError(f"{what}: {named[0][0]} [B,H,W] expected, got {tuple(first.shape)}")
+    for name, t in named[1:]:
+        if t.shape[-3:] != first.shape:
+            raise RuntimeError(f"{what}: {name} does not match {named[0][0]} {tuple(first.shape)}")
+    return [t.contiguous() for _, t in named]
+
+
+def _pinhole(what, K, B, check_skew):
+    if K.shape != (B, 3, 3):
+        raise RuntimeError(f"{what}: K [{B},3,3] expected, got {tuple(K.shape)}")
+    # the one host read of these wrappers; not possible (and skipped) while the
+    # stream is being captured
+    if check_skew and not torch.cuda.is_current_stream_capturing() and bool((K[:, 0, 1] != 0).any()):
+        raise RuntimeError(f"{what}: K has a non-zero skew; the kernels read fx, fy, cx, cy only")
+    return K.contiguous()
+
+
+def clean_depth(depth, grad_max=0.05, depth_max=6.0, crop_h=32, crop_w=32):
+    """The depth cleaning of the reference's sequence loop
+    (scripts/infer_video.py:647-657), one launch: depth [B,H,W] -> [B,H,W] with
+    0 where the squared forward-difference gradient (map zero-padded below and
+    to the right) exceeds grad_max, where depth > depth_max, and inside the
+    top-left and the bottom-right crop_h x crop_w blocks.
+
+    crop_h == 0 or crop_w == 0 means no crop.  In the reference a zero crop
+    blanks the whole map (depth[-0:, -0:] = 0 selects everything); that is a
+    bug and is not reproduced."""
+    lib = _lib.load()
+    require_device(depth, what="clean_depth")
+    (d,) = _maps("clean_depth", ("depth", depth))
+    B, H, W = d.shape
+    out = torch.empty_like(d)
+    check(lib.dro_depth_clean(ptr(d), B, H, W, float(grad_max), float(depth_max), int(crop_h), int(crop_w),
+                              ptr(out), stream_of(d)), "dro_depth_clean")
+    return out
+
+
+def fuse_depths(depth_ref, depth_src, K, extr_ref, extr_src, thres_p_dist=1.0, thres_d_diff=1e-3, thres_view=1,
+                record=False, check_skew=True):
+    """Multi-view geometric consistency filter and depth fusion
+    (reproject_with_depth_batch, check_geometric_consistency_batch and
+    gemo_filter_fusion, scripts/infer_video.py:254-369), one launch for all
+    source views.
+
+    depth_ref [B,H,W], depth_src [S,B,H,W] (1 <= S <= 8), K [B,3,3] (pinhole: a
+    non-zero skew is refused), extr_ref [B,4,4] and extr_src [S,B,4,4] rigid
+    WORLD->CAMERA transforms.  Returns (fused [B,H,W] float32, count [B,H,W]
+    uint8): the number of source views whose reprojection lands within
+    thres_p_dist pixels and thres_d_diff relative depth, and the mean of the
+    reference depth and the consistent reprojected depths where count >=
+    thres_view (0 elsewhere).
+
+    record=True also returns the decisions per view, [S,B,H,W] each: the
+    sampled source pixel (int32, ((y + 32768) << 16) | (x + 32768), or
+    FUSION_OUTSIDE) and the consistency bit (uint8).
+
+    Allocates the outputs only and does not synchronise -- except for the skew
+    check, one host read of K: pass check_skew=False once K is known to be a
+    pinhole (the check is skipped while the stream is being captured)."""
+    lib = _lib.load()
+    require_device(depth_ref, depth_src, K, extr_ref, extr_src, what="fuse_depths")
+    if depth_src.dim() != 4:
+        raise RuntimeError(f"fuse_depths: depth_src [S,B,H,W] expected, got {tuple(depth_src.shape)}")
+    ref, src = _maps("fuse_depths", ("depth_ref", depth_ref), ("depth_src", depth_src))
+    S, (B, H, W) = src.shape[0], ref.shape
+    if not 1 <= S <= FUSION_MAX_VIEWS:
+        raise RuntimeError(f"fuse_depths: 1 <= S <= {FUSION_MAX_VIEWS} source views expected, got {S}")
+    if extr_ref.shape != (B, 4, 4) or extr_src.shape != (S, B, 4, 4):
+        raise RuntimeError("fuse_depths: extr_ref [B,4,4] and extr_src [S,B,4,4] expected")
+    K = _pinhole("fuse_depths", K, B, check_skew)
+    fused = torch.empty_like(ref)
+    count = torch.empty(B, H, W, device=ref.device, dtype=torch.uint8)
+    pixel = torch.empty(S, B, H, W, device=ref.device, dtype=torch.int32) if record else None
+    consistent = torch.empty(S, B, H, W, device=ref.device, dtype=torch.uint8) if record else None
+    check(lib.dro_depth_fusion(ptr(ref), ptr(src), ptr(K), ptr(extr_ref.contiguous()), ptr(extr_src.contiguous()),
+                               S, B, H, W, float(thres_p_dist), float(thres_d_diff), int(thres_view), ptr(count),
+                               ptr(fused), ptr(pixel), ptr(consistent), stream_of(ref)), "dro_depth_fusion")
+    return (fused, count, pixel, consistent) if record else (fused, count)
+
+
+def backproject_points(depth, rgb, K, cam2world, keep_invalid=False, check_skew=True):
+    """Back-projection to a coloured world-space point cloud
+    (scripts/infer_video.py:674-682).  depth [B,H,W], rgb [B,3,H,W] (the
+    float32 images the network saw), K [B,3,3] pinhole, cam2world [B,4,4]
+    rigid.  Returns (xyz [B*H*W,3], colours [B*H*W,3], n): the points of the
+    pixels with depth > 0 packed to the front in frame-major, then row-major
+    pixel order, and their number as an int32 device tensor; the rows from n
+    on are unspecified.  Slicing to n is the caller's one synchronisation:
+    xyz[:int(n)].
+
+    keep_invalid=True keeps every pixel, as the reference does (a pixel
+    without depth becomes a point at the camera centre); n = B*H*W."""
+    lib = _lib.load()
+    require_device(depth, rgb, K, cam2world, what="backproject_points")
+    (d,) = _maps("backproject_points", ("depth", depth))
+    B, H, W = d.shape
+    if rgb.shape != (B, 3, H, W):
+        raise RuntimeError(f"backproject_points: rgb [{B},3,{H},{W}] expected, got {tuple(rgb.shape)}")
+    if cam2world.shape != (B, 4, 4):
+        raise RuntimeError("backproject_points: cam2world [B,4,4] expected")
+    K = _pinhole("backproject_points", K, B, check_skew)
+    xyz = torch.empty(B * H * W, 3, device=d.device, dtype=torch.float32)
+    colours = torch.empty_like(xyz)
+    n = torch.empty((), device=d.device, dtype=torch.int32)
+    ws = None
+    if not keep_invalid:
+        ws = torch.empty(lib.dro_backproject_points_workspace_bytes(B, H, W) // 4 + 1, device=d.device,
+                         dtype=torch.int32)
+    check(lib.dro_backproject_points(ptr(d), ptr(rgb.contiguous()), ptr(K), ptr(cam2world.contiguous()), B, H, W,
+                                     1 if keep_invalid else 0, ptr(xyz), ptr(colours), ptr(n), ptr(ws),
+                                     stream_of(d)), "dro_backproject_points")
+    return xyz, colours, n

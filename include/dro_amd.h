@@ -50,7 +50,7 @@ extern "C" {
 #define DRO_E_MODE (-3)     /* unknown pose/depth mode or option     */
 
 const char* dro_last_error(void);
-int dro_abi_version(void);   /* 10 (additive since, version unchanged: dro_post_process_inv_depth, the evaluation step's flip post-processing); 10: BatchNorm fused into the 3x3 convs (dro_conv2d_bn_forward / dro_conv2d_bn_backward_data, dro_bn_state_bytes); 9: dro_png_decode (GPU PNG inflate + unfilter); 8: dro_convgru_candidate_backward / dro_convgru_gates_backward (the GRU's elementwise stages in the conv data-gradient epilogues); 7: warp-cost forward/backward take ref_layout (channels-last reference maps); 6: photometric calls take clip_loss (and the backward the l1_signs test hook); 5: warp-cost / photometric backward take the `cells` test hook, view synthesis entry points; 4: convex upsample takes the fused add/mul; 3: conv calls take split-bf16 weights (dro_weight_split); 2: dro_adam_step reads its hyper-parameters from device memory */
+int dro_abi_version(void);   /* 10 (additive since, version unchanged: dro_post_process_inv_depth, the evaluation step's flip post-processing; dro_depth_clean / dro_depth_fusion / dro_backproject_points, the sequence reconstruction); 10: BatchNorm fused into the 3x3 convs (dro_conv2d_bn_forward / dro_conv2d_bn_backward_data, dro_bn_state_bytes); 9: dro_png_decode (GPU PNG inflate + unfilter); 8: dro_convgru_candidate_backward / dro_convgru_gates_backward (the GRU's elementwise stages in the conv data-gradient epilogues); 7: warp-cost forward/backward take ref_layout (channels-last reference maps); 6: photometric calls take clip_loss (and the backward the l1_signs test hook); 5: warp-cost / photometric backward take the `cells` test hook, view synthesis entry points; 4: convex upsample takes the fused add/mul; 3: conv calls take split-bf16 weights (dro_weight_split); 2: dro_adam_step reads its hyper-parameters from device memory */
 
 /* In-graph step timeline (diagnostics, tools/step_timeline.py): record the
  * device's constant-rate real-time counter into buf[slot] when `stream`
@@ -312,6 +312,57 @@ int dro_depth_metrics_demon_reduce(const float* gt, const float* pred_up, const 
  * B 1..65535, W >= 2. */
 int dro_post_process_inv_depth(const float* inv, const float* inv_flipped, int B, int H, int W,
                                int method, float* inv_pp, float* depth, float* depth_pp, void* stream);
+
+/* ------------------------------------------------------------------------
+ * Sequence reconstruction (scripts/infer_video.py of the reference): cleaned
+ * depth maps -> multi-view consistency filter and fusion -> packed point cloud.
+ * All maps fp32 [B,H,W] with H, W >= 2.  K [B,3,3] is read as a pinhole (fx,
+ * fy, cx, cy).  Thresholds that are negative or NaN give DRO_E_MODE.
+ * ---------------------------------------------------------------------- */
+
+/* infer_video.py:647-657.  g = (d[y+1,x] - d[y,x])^2 + (d[y,x+1] - d[y,x])^2 on
+ * the map zero-padded below and to the right; out = 0 where g > grad_max, or
+ * d > depth_max, or the pixel lies in the top-left or in the bottom-right
+ * crop_h x crop_w block, else d (both tests on the input values; out may not
+ * alias depth).  crop_h == 0 or crop_w == 0: no crop (the reference's
+ * depth[-0:, -0:] = 0 blanks the whole map; not reproduced). */
+int dro_depth_clean(const float* depth, int B, int H, int W, float grad_max, float depth_max, int crop_h,
+                    int crop_w, float* out, void* stream);
+
+/* reproject_with_depth_batch, check_geometric_consistency_batch and the sums
+ * of gemo_filter_fusion (infer_video.py:254-369) for all S source views in one
+ * launch.  depth_ref [B,H,W], depth_src [S,B,H,W], extr_ref [B,4,4] and
+ * extr_src [S,B,4,4] rigid WORLD->CAMERA matrices (row-major; the last row is
+ * not read), 1 <= S <= 8.  Per view, with M = E_src E_ref^-1 (rigid inverse
+ * formed in the kernel): the pixel (x, y, d) is lifted, moved by M and
+ * projected (z clamped at 1e-10) to (u, v); the source depth is sampled at the
+ * nearest pixel (round half to even, 0 outside the map); the unrounded (u, v)
+ * with that depth is lifted, moved by M^-1, d_re = z [sampled > 0], and
+ * projected to (u_re, v_re).  The view is consistent iff
+ * |(u_re, v_re) - (x, y)| < thres_p_dist and |d_re - d| / max(d, 1e-10) <
+ * thres_d_diff (a NaN is inconsistent).
+ * count [B,H,W] uint8: consistent views; fused [B,H,W]: (sum of the consistent
+ * d_re + d) / (count + 1) where count >= thres_view, else 0.
+ * Test hooks, NULL in production, [S,B,H,W] each: rec_pixel the sampled source
+ * pixel ((y + 32768) << 16 | (x + 32768), -2 when outside the map),
+ * rec_consistent the consistency bit. */
+int dro_depth_fusion(const float* depth_ref, const float* depth_src, const float* K, const float* extr_ref,
+                     const float* extr_src, int S, int B, int H, int W, float thres_p_dist, float thres_d_diff,
+                     int thres_view, unsigned char* count, float* fused, int* rec_pixel,
+                     unsigned char* rec_consistent, void* stream);
+
+/* infer_video.py:674-682.  depth [B,H,W], rgb [B,3,H,W], cam2world [B,4,4]
+ * (rigid, row-major) -> xyz [B*H*W,3], rgb_out [B*H*W,3], *n (device int32).
+ * The points of the pixels with depth > 0 are packed to the front in
+ * frame-major, then row-major pixel order (deterministic: block counts and
+ * wave ballots, no atomics); the rows from *n on are left unwritten.
+ * keep_invalid != 0: every pixel gives a point (a non-positive depth one at
+ * the camera centre, as in the reference), *n = B*H*W, workspace may be NULL.
+ * B*H*W < 2^31. */
+size_t dro_backproject_points_workspace_bytes(int B, int H, int W);
+int dro_backproject_points(const float* depth, const float* rgb, const float* K, const float* cam2world, int B,
+                           int H, int W, int keep_invalid, float* xyz, float* rgb_out, int* n, void* workspace,
+                           void* stream);
 
 /* Resize + ToTensor of decoded uint8 RGB frames, bit-identical to Pillow's
  * BILINEAR resampling (torchvision Resize on PIL images, datasets/
