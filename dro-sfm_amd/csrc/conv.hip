@@ -3074,7 +3074,7 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
     const IgPlan gp = plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W, gap->wcin);
     const long long T = (long long)KH * KW;
     if (gap->gap_at < 0 || gap->gap_len < 0 || gap->gap_at > a.g.Cin || a.g.Cin + gap->gap_len > gap->wcin ||
-        grad_weight || wsplit || gf || !gp.halo || gap->gap_at % gp.bm != 0 || (gap->gap_len * T) % 4 != 0) {
+        grad_weight || gf || !gp.halo || gap->gap_at % gp.bm != 0 || (gap->gap_len * T) % 4 != 0) {
       set_error("conv2d_backward_gapped: needs a halo-kernel data gradient (1x1, 1x5, 5x1, 3x3; weight rows "
                 "and the gap multiples of 4 floats), the gap at a row-tile boundary inside the weight row");
       return DRO_E_SHAPE;
@@ -3126,7 +3126,6 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
     a.gsrc_ctot[0] = Cout;
     a.gsrc_coff[0] = 0;
     a.gsrc_acc[0] = 1;
-    a.wsplit = nullptr;   // the split-bf16 engine has no GRU epilogues
   } else if (gf) {   // kind 4: source 0 is this half's h (hd = Cout / 2 channels), accumulated
     const int hd = Cout / 2;
     if (!gf->zr || !gf->h || !gf->dzr || !gf->dh || !gf->q || !gf->dq || !a.gsrc[0]) {
@@ -3148,7 +3147,6 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
     a.g1dh = gf->dh;
     a.g1acc = gf->dh_acc ? 1 : 0;
     a.gsrc_acc[0] = 1;
-    a.wsplit = nullptr;
   }
   a.weight = weight;
   a.gweight = grad_weight;

@@ -451,11 +451,7 @@ XPlan plan_xconv(int rows, int kch, int KH, int KW, int B, int H, int W) {
   pl.nck = (kch + 31) / 32;
   const long long blocks = (long long)pl.row_tiles * pl.ptiles;
   int ks = 1;
-  static const long long short_grid = [] {   // tuning: grids below this many tiles split K over blocks
-    const char* e = getenv("DRO_XCONV_SPLIT_BELOW");
-    return e ? atoll(e) : 128LL;
-  }();
-  if (blocks < short_grid) {
+  if (blocks < 128) {   // grids below this many tiles split K over blocks
     ks = (int)((256 + blocks - 1) / blocks);
     if (ks > 16) ks = 16;
     if (ks > pl.nck) ks = pl.nck;

@@ -136,28 +136,22 @@ def weight_grad_scope():
 
 
 # measured: not faster than the f32 engine at the step's shapes;
-# DRO_SPLIT_ENGINE=all|3x3fwd turns it on for A/B runs
-_XCONV = [os.environ.get("DRO_SPLIT_ENGINE", "") in ("all", "3x3fwd")]
+# no environment variable or config turns it on, only set_split_engine
+_XCONV = [False]
 _XSHAPES = {(1, 5), (5, 1), (3, 3), (1, 1)}
-# "all": every xconv shape, fwd + data grad; "3x3fwd": 3x3 forwards only
-_XPOLICY = [os.environ.get("DRO_SPLIT_ENGINE", "") or "all"]
 _SPLITS = {}       # (data_ptr, shape, device) -> [generation, fwd split, bwd split]
 
 
-def set_split_engine(enabled, policy="all"):
+def set_split_engine(enabled):
     """Split-bf16 MFMA engine for the halo convs (True) or the f32-MFMA engine
-    (False, default: the faster of the two at the update-block shapes).
-    policy "3x3fwd" limits it to the forward of the 3x3 convs."""
+    (False, default: the faster of the two at the update-block shapes)."""
     _XCONV[0] = bool(enabled)
-    _XPOLICY[0] = policy
 
 
 def _wsplit(weight):
     """(fwd, bwd) split-bf16 copies of a contiguous weight for the xconv engine,
     or (None, None) when the f32 engine runs this conv."""
     if not _XCONV[0] or tuple(weight.shape[2:]) not in _XSHAPES:
-        return None, None
-    if _XPOLICY[0] == "3x3fwd" and tuple(weight.shape[2:]) != (3, 3):
         return None, None
     lib = _lib.load()
     Cout, Cin, KH, KW = weight.shape
@@ -175,8 +169,6 @@ def _wsplit(weight):
         check(lib.dro_weight_split(ptr(weight), Cout, Cin, KH, KW, ptr(ent[1]), ptr(ent[2]),
                                    stream_of(weight)), "dro_weight_split")
         ent[0] = _GEN[0]
-    if _XPOLICY[0] == "3x3fwd":
-        return ent[1], None
     return ent[1], ent[2]
 
 
@@ -186,7 +178,7 @@ def _wsplit_bwd(weight):
     engine.  setup_context reads it here instead of from the forward's
     side channel (a module-global hand-off breaks when tracing
     runs a setup without its implementation)."""
-    if not _XCONV[0] or _XPOLICY[0] == "3x3fwd" or not weight.is_contiguous():
+    if not _XCONV[0] or not weight.is_contiguous():
         return None
     ent = _SPLITS.get((weight.data_ptr(), tuple(weight.shape), weight.device))
     return ent[2] if ent is not None and ent[0] == _GEN[0] else None
