@@ -11,6 +11,10 @@ float32 [N, H, W] = value / 256 with -1 where the value is 0 (read_png_depth).
 Supported: non-interlaced 8-bit grey / RGB / RGBA and 16-bit grey -- every
 PNG the reference's KITTI / NYU / ScanNet readers open; anything else raises
 (no CPU fallback).
+
+encode_png is the host-side writer of the files the package itself produces
+(utils/depth.py::write_depth, models/infer.py): chunks and zlib only, the
+scanlines come from the caller.
 """
 import struct
 import zlib
@@ -70,6 +74,26 @@ def parse_png(data):
         raise NotImplementedError(f"PNG bit depth {depth}, colour type {ctype}, interlace {interlace}: only "
                                   "non-interlaced 8-bit grey / RGB / RGBA and 16-bit grey are decoded on the GPU")
     return PngInfo(w, h, kind, b"".join(idat))
+
+
+def _chunk(typ, body):
+    return struct.pack(">I", len(body)) + typ + body + struct.pack(">I", zlib.crc32(typ + body) & 0xFFFFFFFF)
+
+
+def encode_png(rows, width, height, kind, level=6):
+    """The bytes of a non-interlaced PNG from its filtered scanlines (host
+    code): `rows` is height x (1 + width * bytes per pixel) bytes -- a filter
+    type byte, then the pixels, 16-bit samples big-endian (uint8 array or
+    bytes; hip.depth_png16_rows makes them for a depth map).  kind: 0 grey8,
+    2 RGB8, 6 RGBA8, 16 grey16.  Signature, IHDR, one IDAT (zlib), IEND."""
+    fmt = {k: dc for dc, k in KINDS.items()}.get(kind)
+    if fmt is None:
+        raise ValueError(f"encode_png: kind {kind!r} (0 grey8, 2 RGB8, 6 RGBA8, 16 grey16)")
+    raw = rows.tobytes() if hasattr(rows, "tobytes") else bytes(rows)
+    if width < 1 or height < 1 or len(raw) != height * (1 + width * _bpp(kind)):
+        raise ValueError(f"encode_png: {len(raw)} bytes are not {height} rows of 1 + {width} x {_bpp(kind)}")
+    ihdr = struct.pack(">IIBBBBB", width, height, fmt[0], fmt[1], 0, 0, 0)
+    return _SIG + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(raw, level)) + _chunk(b"IEND", b"")
 
 
 def _bpp(kind):

@@ -82,6 +82,9 @@ def load():
     _sig(lib.dro_depth_fusion, P, P, P, P, P, I, I, I, I, F, F, I, P, P, P, P, S)
     _sig(lib.dro_backproject_points_workspace_bytes, I, I, I, restype=Z)
     _sig(lib.dro_backproject_points, P, P, P, P, I, I, I, I, P, P, P, P, S)
+    _sig(lib.dro_percentile, P, I, LL, ctypes.c_double, I, P, S)
+    _sig(lib.dro_colorize, P, P, P, P, I, I, I, P, P, S)
+    _sig(lib.dro_depth_png16_rows, P, I, I, I, P, S)
     _sig(lib.dro_resize_rgb8_to_tensor, P, I, I, I, I, I, P, P, I, P, P, I, P, P, S)
     _sig(lib.dro_color_jitter_rgb8, P, I, I, I, P, P, S)
     _sig(lib.dro_resize_rgb8, P, I, I, I, I, I, P, P, I, P, P, I, P, P, S)
@@ -156,6 +159,7 @@ EXPORTED = (
     "dro_conv2d_weight_grad_group", "dro_conv2d_weight_grad_multi_ex", "dro_conv2d_weight_grad_group_ex",
     "dro_gru_backward_elem", "dro_convgru_candidate_backward", "dro_convgru_gates_backward", "dro_adam_step",
     "dro_bn_state_bytes", "dro_bn_apply", "dro_bn_backward_apply", "dro_conv2d_bn_forward", "dro_conv2d_bn_backward_data",
+    "dro_percentile", "dro_colorize", "dro_depth_png16_rows",
 )
 
 

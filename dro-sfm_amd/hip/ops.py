@@ -1383,3 +1383,63 @@ def backproject_points(depth, rgb, K, cam2world, keep_invalid=False, check_skew=
                                      1 if keep_invalid else 0, ptr(xyz), ptr(colours), ptr(n), ptr(ws),
                                      stream_of(d)), "dro_backproject_points")
     return xyz, colours, n
+
+
+# ----------------------------------------------------------------------------
+# depth inference outputs (csrc/viz.hip)
+# ----------------------------------------------------------------------------
+def percentile(values, q, filter_zeros=False):
+    """np.percentile(row, q) (numpy's default, linear) of each row of values
+    [B,n] -> [B], on the device: one launch whatever B, no host round trip,
+    bitwise deterministic.  filter_zeros keeps only the values > 0 of a row
+    (viz_inv_depth's `inv_depth[inv_depth > 0]`); a row without any gives NaN.
+    Values must be finite."""
+    lib = _lib.load()
+    require_device(values, what="percentile")
+    if values.dim() != 2 or values.shape[1] < 1:
+        raise RuntimeError(f"percentile: values [B,n>=1] expected, got {tuple(values.shape)}")
+    v = values.contiguous()
+    B, n = v.shape
+    out = torch.empty(B, device=v.device, dtype=torch.float32)
+    check(lib.dro_percentile(ptr(v), B, n, float(q), 1 if filter_zeros else 0, ptr(out), stream_of(v)),
+          "dro_percentile")
+    return out
+
+
+def colorize(x, norm, lut, rgb=None, color=True):
+    """Colour-map lookup of x / (norm + 1e-6), matplotlib's rules for a
+    256-entry table: x [B,H,W], norm [B] (device), lut [256,3] -> color
+    [B,H,W,3] float32; a NaN quotient gives (0,0,0).  With rgb [B,3,H,W] also
+    the uint8 panel [B,2H,W,3]: the frame above the colour map, both
+    rint(255 v) saturated.  Returns color, or (color, panel); color=False
+    (with rgb) skips the float output and returns (None, panel).  One launch."""
+    lib = _lib.load()
+    require_device(x, norm, lut, rgb, what="colorize")
+    (x,) = _maps("colorize", ("x", x))
+    B, H, W = x.shape
+    if norm.shape != (B,) or lut.shape != (256, 3):
+        raise RuntimeError(f"colorize: norm [{B}] and lut [256,3] expected, got {tuple(norm.shape)} and "
+                           f"{tuple(lut.shape)}")
+    if rgb is not None and rgb.shape != (B, 3, H, W):
+        raise RuntimeError(f"colorize: rgb [{B},3,{H},{W}] expected, got {tuple(rgb.shape)}")
+    if rgb is None and not color:
+        raise RuntimeError("colorize: nothing to compute (color=False without rgb)")
+    out = torch.empty(B, H, W, 3, device=x.device, dtype=torch.float32) if color else None
+    panel = torch.empty(B, 2 * H, W, 3, device=x.device, dtype=torch.uint8) if rgb is not None else None
+    check(lib.dro_colorize(ptr(x), ptr(norm.contiguous()), ptr(lut.contiguous()),
+                           ptr(rgb.contiguous() if rgb is not None else None), B, H, W, ptr(out), ptr(panel),
+                           stream_of(x)), "dro_colorize")
+    return out if rgb is None else (out, panel)
+
+
+def depth_png16_rows(depth):
+    """depth [B,H,W] -> uint8 [B,H,1+2W]: the scanlines of the KITTI-style
+    16-bit depth PNG (filter byte 0, big-endian clamp(trunc(depth * 256), 0,
+    65535); NaN and negatives 0), ready for datasets.png.encode_png."""
+    lib = _lib.load()
+    require_device(depth, what="depth_png16_rows")
+    (d,) = _maps("depth_png16_rows", ("depth", depth))
+    B, H, W = d.shape
+    rows = torch.empty(B, H, 1 + 2 * W, device=d.device, dtype=torch.uint8)
+    check(lib.dro_depth_png16_rows(ptr(d), B, H, W, ptr(rows), stream_of(d)), "dro_depth_png16_rows")
+    return rows

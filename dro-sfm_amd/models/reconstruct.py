@@ -125,6 +125,24 @@ def fuse_sequence(depths, K, cam2world, params, check_skew=True):
     return torch.cat([depths[:S], fused])
 
 
+def predict_interior_frames(model, frames, K1, frames_per_forward, what):
+    """Every interior frame t = 1..T-2 of frames [T,3,H,W] through `model`
+    with the references (t-1, t+1), frames_per_forward frames per forward.
+    Returns (inv_depths [T-2,1,H,W], relative poses [T-2,2,6] or [T-2,2,4,4],
+    see _pose_tensor).  The caller sets eval mode and no_grad."""
+    T = frames.shape[0]
+    inv, poses = [], []
+    for lo in range(1, T - 1, frames_per_forward):
+        hi = min(lo + frames_per_forward, T - 1)
+        out = model({"rgb": frames[lo:hi], "rgb_context": [frames[lo - 1:hi - 1], frames[lo + 1:hi + 1]],
+                     "intrinsics": K1.expand(hi - lo, 3, 3).contiguous()})
+        inv.append(out["inv_depths"][0])
+        if len(out["poses"]) != 2:
+            raise RuntimeError(f"{what}: the model must predict the two context poses")
+        poses.append(_pose_tensor(out["poses"]))
+    return torch.cat(inv), torch.cat(poses)
+
+
 def reconstruct_sequence(model, frames, K, params=None, fuse=True, keep_invalid=False, frames_per_forward=4):
     """frames [T,3,H,W] float32 on the GPU (T >= 3), K [3,3] or [1,3,3] pinhole
     intrinsics of those frames.  Every interior frame t = 1..T-2 is predicted
@@ -150,18 +168,10 @@ def reconstruct_sequence(model, frames, K, params=None, fuse=True, keep_invalid=
     model.eval()
     try:
         with torch.no_grad():
-            inv, poses = [], []
-            for lo in range(1, T - 1, frames_per_forward):
-                hi = min(lo + frames_per_forward, T - 1)
-                out = model({"rgb": frames[lo:hi], "rgb_context": [frames[lo - 1:hi - 1], frames[lo + 1:hi + 1]],
-                             "intrinsics": K1.expand(hi - lo, 3, 3).contiguous()})
-                inv.append(out["inv_depths"][0])
-                if len(out["poses"]) != 2:
-                    raise RuntimeError("reconstruct_sequence: the model must predict the two context poses")
-                poses.append(_pose_tensor(out["poses"]))
-            depths = hip.clean_depth(inv2depth(torch.cat(inv))[:, 0], params.grad_max, params.depth_max,
+            inv, poses = predict_interior_frames(model, frames, K1, frames_per_forward, "reconstruct_sequence")
+            depths = hip.clean_depth(inv2depth(inv)[:, 0], params.grad_max, params.depth_max,
                                      params.crop_h, params.crop_w)
-            rel = relative_poses_to_host(torch.cat(poses))
+            rel = relative_poses_to_host(poses)
             cam2world = chain_poses(rel[:, 0], rel[:, 1])
             Kn = K1.expand(n, 3, 3).contiguous()
             if fuse:

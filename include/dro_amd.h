@@ -364,6 +364,37 @@ int dro_backproject_points(const float* depth, const float* rgb, const float* K,
                            int H, int W, int keep_invalid, float* xyz, float* rgb_out, int* n, void* workspace,
                            void* stream);
 
+/* ------------------------------------------------------------------------
+ * Depth inference outputs (viz_inv_depth and write_depth, dro_sfm/utils/
+ * depth.py:34-99 of the reference, and the RGB-over-depth panel of
+ * scripts/infer.py:160-181).  B 1..65535; images H, W >= 1, H*W < 2^31.
+ * ---------------------------------------------------------------------- */
+
+/* numpy's default (linear) percentile of each row of values [B,n], 1 <= n <
+ * 2^31, q in [0,100] (else DRO_E_MODE); filter_zeros != 0 keeps only x > 0.
+ * With m kept values, v = (m-1) q / 100 in double, lo = floor(v), hi =
+ * min(lo+1, m-1): out[b] = a[lo] + (a[hi] - a[lo]) (v - lo) on the exact order
+ * statistics (evaluated in double, rounded once); m == 0 gives NaN.  Negative
+ * values and -0.0 order correctly; inputs must be finite.  One launch, one
+ * block per row (radix select), no workspace, no host round trip; integer
+ * counts only, so results are bitwise deterministic. */
+int dro_percentile(const float* values, int B, long long n, double q, int filter_zeros, float* out,
+                   void* stream);
+
+/* x [B,H,W], norm [B] (device), lut [256,3] -> color [B,H,W,3] fp32 =
+ * lut[min(int(clip(x / (norm + 1e-6), 0, 1) * 256), 255)], (0,0,0) where the
+ * quotient is NaN: matplotlib's lookup of a 256-entry ListedColormap.
+ * panel [B,2H,W,3] uint8 (nullable; needs rgb [B,3,H,W]): rint(255 rgb)
+ * saturated above rint(255 color), half to even.  color may be NULL when
+ * panel is given.  One launch. */
+int dro_colorize(const float* x, const float* norm, const float* lut, const float* rgb, int B, int H, int W,
+                 float* color, unsigned char* panel, void* stream);
+
+/* depth [B,H,W] -> rows [B,H,1+2W] bytes: the scanlines of a 16-bit greyscale
+ * PNG ready for deflate -- filter byte 0, then big-endian uint16 of
+ * clamp(trunc(depth * 256), 0, 65535); NaN and negatives give 0. */
+int dro_depth_png16_rows(const float* depth, int B, int H, int W, unsigned char* rows, void* stream);
+
 /* Resize + ToTensor of decoded uint8 RGB frames, bit-identical to Pillow's
  * BILINEAR resampling (torchvision Resize on PIL images, datasets/
  * augmentations.py:69-111, then ToTensor :149-160 of the reference).
