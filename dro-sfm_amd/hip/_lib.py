@@ -82,6 +82,8 @@ def load():
     _sig(lib.dro_depth_fusion, P, P, P, P, P, I, I, I, I, F, F, I, P, P, P, P, S)
     _sig(lib.dro_backproject_points_workspace_bytes, I, I, I, restype=Z)
     _sig(lib.dro_backproject_points, P, P, P, P, I, I, I, I, P, P, P, P, S)
+    _sig(lib.dro_render_points_workspace_bytes, I, I, I, I, restype=Z)
+    _sig(lib.dro_render_points, P, P, LL, P, P, P, I, I, I, I, F, ctypes.c_uint, P, P, P, P, P, P, Z, S)
     _sig(lib.dro_percentile, P, I, LL, ctypes.c_double, I, P, S)
     _sig(lib.dro_colorize, P, P, P, P, I, I, I, P, P, S)
     _sig(lib.dro_depth_png16_rows, P, I, I, I, P, S)
@@ -146,6 +148,7 @@ EXPORTED = (
     "dro_depth_metrics_reduce", "dro_depth_metrics_median_workspace_bytes", "dro_depth_metrics_median",
     "dro_depth_metrics_demon_prepare", "dro_depth_metrics_demon_reduce", "dro_post_process_inv_depth",
     "dro_depth_clean", "dro_depth_fusion", "dro_backproject_points_workspace_bytes", "dro_backproject_points",
+    "dro_render_points_workspace_bytes", "dro_render_points",
     "dro_conv2d_strided_workspace_bytes", "dro_conv2d_strided_forward", "dro_conv2d_strided_backward",
     "dro_pose_mean_forward", "dro_pose_mean_backward",
     "dro_resize_rgb8_to_tensor", "dro_color_jitter_rgb8", "dro_resize_rgb8", "dro_rgb8_to_tensor",

@@ -1386,6 +1386,74 @@ def backproject_points(depth, rgb, K, cam2world, keep_invalid=False, check_skew=
 
 
 # ----------------------------------------------------------------------------
+# point-cloud rendering (csrc/render.hip)
+# ----------------------------------------------------------------------------
+RENDER_MAX_POINT_SIZE = 15
+RENDER_REJECTED = -1         # render_points(record=True): the (view, point) pair wrote no key
+
+
+def render_points(xyz, rgb, K, world2cam, size, limit=None, point_size=1, near=1e-6, background=(0, 0, 0),
+                  want_depth=False, want_index=False, record=False, check_skew=True):
+    """The cloud xyz [n,3] with colours rgb [n,3] (float, 0..1) drawn from V
+    cameras at once: K [V,3,3] pinhole (a non-zero skew is refused), world2cam
+    [V,4,4] rigid WORLD->CAMERA, size = (H, W).  Integer pixel coordinates are
+    pixel centres (the convention backproject_points lifts with).  Every point
+    with z >= near whose pixel lies on the image (or within point_size // 2 of
+    it) paints a point_size x point_size square; the nearest point wins a
+    pixel, the lowest index among equal depths.  limit [V] int32 (device): view
+    v draws the points 0 .. limit[v]-1 only.
+
+    Returns image [V,H,W,3] uint8 (rint(255 rgb) saturated, `background`
+    elsewhere); with want_depth / want_index / record a tuple (image, depth
+    [V,H,W] float32 or None, index [V,H,W] int32 or None[, pixel [V,n] int32,
+    zbits [V,n] int32]): depth 0 and index -1 where nothing was drawn; the
+    recorded z-buffer cell ((y + m) (W + 2m) + (x + m), m = point_size // 2, or
+    RENDER_REJECTED) and the bits of z per (view, point).
+
+    A software z-buffer (fill, splat with one 64-bit atomicMin per point and
+    view, window-minimum resolve), bitwise deterministic.  Allocates the
+    outputs and the z-buffer and does not synchronise -- except for the skew
+    check, one host read of K: pass check_skew=False once K is known to be a
+    pinhole (the check is skipped while the stream is being captured)."""
+    lib = _lib.load()
+    require_device(xyz, rgb, K, world2cam, what="render_points")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+        raise RuntimeError(f"render_points: xyz and rgb [n,3] expected, got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+    if world2cam.dim() != 3 or world2cam.shape[1:] != (4, 4):
+        raise RuntimeError(f"render_points: world2cam [V,4,4] expected, got {tuple(world2cam.shape)}")
+    n, V = xyz.shape[0], world2cam.shape[0]
+    H, W = (int(v) for v in size)
+    s = int(point_size)
+    if not 1 <= s <= RENDER_MAX_POINT_SIZE:
+        raise RuntimeError(f"render_points: 1 <= point_size <= {RENDER_MAX_POINT_SIZE} expected, got {point_size}")
+    if V < 1 or H < 1 or W < 1:
+        raise RuntimeError(f"render_points: V, H, W >= 1 expected, got {V}, {H}, {W}")
+    if limit is not None:
+        if not limit.is_cuda or limit.dtype != torch.int32 or limit.shape != (V,):
+            raise RuntimeError(f"render_points: limit [{V}] int32 on the device expected")
+        limit = limit.contiguous()
+    bg = [int(c) for c in background]
+    if len(bg) != 3 or any(not 0 <= c <= 255 for c in bg):
+        raise RuntimeError(f"render_points: background of three bytes expected, got {background}")
+    K = _pinhole("render_points", K, V, check_skew)
+    dev = xyz.device
+    image = torch.empty(V, H, W, 3, device=dev, dtype=torch.uint8)
+    depth = torch.empty(V, H, W, device=dev, dtype=torch.float32) if want_depth else None
+    index = torch.empty(V, H, W, device=dev, dtype=torch.int32) if want_index else None
+    pixel = torch.empty(V, n, device=dev, dtype=torch.int32) if record else None
+    zbits = torch.empty(V, n, device=dev, dtype=torch.int32) if record else None
+    nbytes = lib.dro_render_points_workspace_bytes(V, H, W, s)
+    ws = torch.empty(max(nbytes // 8, 1), device=dev, dtype=torch.int64)
+    check(lib.dro_render_points(ptr(xyz.contiguous()), ptr(rgb.contiguous()), n, ptr(K), ptr(world2cam.contiguous()),
+                                ptr(limit), V, H, W, s, float(near), bg[0] | bg[1] << 8 | bg[2] << 16, ptr(image),
+                                ptr(depth), ptr(index), ptr(pixel), ptr(zbits), ptr(ws), nbytes, stream_of(xyz)),
+          "dro_render_points")
+    if not (want_depth or want_index or record):
+        return image
+    return (image, depth, index, pixel, zbits) if record else (image, depth, index)
+
+
+# ----------------------------------------------------------------------------
 # depth inference outputs (csrc/viz.hip)
 # ----------------------------------------------------------------------------
 def percentile(values, q, filter_zeros=False):

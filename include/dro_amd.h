@@ -365,6 +365,37 @@ int dro_backproject_points(const float* depth, const float* rgb, const float* K,
                            void* stream);
 
 /* ------------------------------------------------------------------------
+ * Point-cloud rendering (the picture of scripts/vis.py:259-360 of the
+ * reference: the cloud as square points on a plain background), a software
+ * z-buffer instead of vtk's OpenGL output.  fp32, three launches (fill, splat,
+ * resolve) for all V views, bitwise deterministic.
+ *
+ * xyz [n,3], rgb [n,3] float (0 <= n <= 2^31 - 1; both may be NULL when n is
+ * 0), K [V,3,3] (read as a pinhole), world2cam [V,4,4] rigid (row-major, the
+ * last row is not read), limit [V] device int32 (nullable): view v draws the
+ * points 0 .. limit[v]-1.  V 1..65535, H, W 1..32768, point_size s 1..15,
+ * near > 0 and finite (else DRO_E_MODE), background = r | g << 8 | b << 16.
+ * A point is drawn iff its camera point (x, y, z) = R p + t is finite with
+ * z >= near and its pixel (rintf(fx x / z + cx), rintf(fy y / z + cy)) --
+ * integer coordinates are pixel centres, halves go to even -- lies within
+ * m = s / 2 pixels of the image; it covers the pixels -(s/2) .. +((s-1)/2)
+ * around that centre.  A pixel shows, of the points covering it, the one with
+ * the smallest z, and among equal z the lowest index.
+ * image [V,H,W,3] uint8: rint(255 rgb) saturated, half to even (NaN -> 0), or
+ * the background; depth [V,H,W] (nullable): z, 0 where nothing was drawn;
+ * index [V,H,W] int32 (nullable): the point, -1 where nothing was drawn.
+ * workspace: dro_render_points_workspace_bytes = 8 V (H + 2m)(W + 2m) bytes
+ * (the padded z-buffer of 64-bit keys; 0 for sizes out of range).
+ * Test hooks, NULL in production, [V,n] each: rec_pixel the padded z-buffer
+ * cell (y + m)(W + 2m) + (x + m) the pair wrote its key to, -1 when it wrote
+ * none; rec_zbits the bits of z (0 when none). */
+size_t dro_render_points_workspace_bytes(int V, int H, int W, int point_size);
+int dro_render_points(const float* xyz, const float* rgb, long long n, const float* K, const float* world2cam,
+                      const int* limit, int V, int H, int W, int point_size, float near, unsigned int background,
+                      unsigned char* image, float* depth, int* index, int* rec_pixel, unsigned int* rec_zbits,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Depth inference outputs (viz_inv_depth and write_depth, dro_sfm/utils/
  * depth.py:34-99 of the reference, and the RGB-over-depth panel of
  * scripts/infer.py:160-181).  B 1..65535; images H, W >= 1, H*W < 2^31.
