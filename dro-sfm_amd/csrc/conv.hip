@@ -2067,12 +2067,19 @@ size_t fwd_workspace(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
                   xconv_part_bytes(Cout, Cin, KH, KW, B, H, W));
 }
 
+// split-K partials of the data gradient (either engine): the backward
+// workspace's middle section -- bwd_workspace sizes it and
+// conv2d_backward_impl places the weight-gradient partials after it
+size_t dgrad_part_bytes(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
+  return std::max(plan_igemm(Cin, Cout, KH, KW, B, H, W, Cin).part_bytes,
+                  xconv_part_bytes(Cin, Cout, KH, KW, B, H, W));
+}
+
 size_t bwd_workspace(int B, int H, int W, int Cin, int Cout, int KH, int KW) {
   const long long P = (long long)B * H * W;
   const int T = KH * KW;
   return align256((size_t)Cout * P * sizeof(float)) +              // pre-activation gradient
-         std::max(plan_igemm(Cin, Cout, KH, KW, B, H, W, Cin).part_bytes,  // data-gradient split-K
-                  xconv_part_bytes(Cin, Cout, KH, KW, B, H, W)) +
+         dgrad_part_bytes(B, H, W, Cin, Cout, KH, KW) +            // data-gradient split-K
          std::max(plan_wgrad(Cin, Cout, T, P).part_bytes,                   // weight-gradient partials
                   plan_wgrad2(Cin, Cout, KH, KW, 1, B, H, W).part_bytes);
 }
@@ -3159,8 +3166,7 @@ static int conv2d_backward_impl(const dro_slice* srcs, int nsrc, const float* we
   char* ws = static_cast<char*>(workspace);
   char* ws_pre = ws;
   char* ws_ig = ws_pre + align256((size_t)Cout * P * sizeof(float));
-  char* ws_wg = ws_ig + std::max(plan_igemm(a.g.Cin, Cout, KH, KW, B, H, W, a.g.Cin).part_bytes,
-                                 xconv_part_bytes(a.g.Cin, Cout, KH, KW, B, H, W));
+  char* ws_wg = ws_ig + dgrad_part_bytes(B, H, W, a.g.Cin, Cout, KH, KW);
   // fold the activation derivative into the halo kernels' G staging when both
   // gradients run there (dense y); otherwise form G first
   const WhPlan wh = plan_wgrad2(a.g.Cin, Cout, KH, KW, 1, B, H, W);
