@@ -21,6 +21,8 @@
 // Layout: NCHW fp32, planes of HW contiguous floats.
 #include "dro_common.hpp"
 
+#include <math.h>
+
 namespace dro {
 namespace {
 
@@ -408,6 +410,64 @@ int bn_check(int N, int C, int HW) {
 
 bool aligned16(const void* p) { return p == nullptr || (reinterpret_cast<size_t>(p) & 15) == 0; }
 
+// ---------------------------------------------------------------- eval mode
+// y = act((x - running_mean) * (gamma / sqrt(running_var + eps)) + beta [+ skip]):
+// F.batch_norm(training=False) with the residual add and the ReLU that follow
+// it, one launch, 8 (12 with a skip) bytes per element.  The statistics are
+// read on every launch -- nothing is folded on the host, so a replayed graph
+// follows running statistics and weights that were updated in place.  The
+// channel is uniform over the block: its four constants are scalar loads and
+// k is formed once per wave, not per element.
+struct BnEvalArgs {
+  const float* x;
+  const float* gamma;      // nullable with beta: 1 and 0
+  const float* beta;
+  const float* mean;
+  const float* var;
+  const float* skip;       // nullable
+  float* y;
+  int relu;
+  float eps;
+  int C, HW;
+  int per;                 // blocks per plane
+  long long items;         // planes * per
+};
+
+constexpr int kBnEvalMaxBlocks = 1 << 20;   // grid.x <= 2^31 - 1 and grid * block < 2^32 (HIP's limits)
+
+// 1-D grid of min(items, kBnEvalMaxBlocks) blocks over the planes * per work
+// items: item t is part t % per of plane t / per, and a plane is grid-strided
+// over by its per parts; a block takes items blockIdx.x, + gridDim.x, ...
+template <bool VEC>
+__global__ __launch_bounds__(kBnThreads) void bn_eval_kernel(BnEvalArgs a) {
+  const float* __restrict__ x = a.x;
+  const float* __restrict__ skip = a.skip;
+  float* __restrict__ y = a.y;
+  const int hw4 = a.HW & ~3;
+  // 64-bit counters: i + stride may pass 2^31 when one plane holds nearly 2^31 floats
+  const long long stride = (long long)kBnThreads * a.per;
+  for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
+    const long long plane = item / a.per;
+    const int part = (int)(item - plane * a.per);
+    const int c = (int)(plane % a.C);
+    const float mu = a.mean[c];
+    const float k = (a.gamma ? a.gamma[c] : 1.f) / sqrtf(a.var[c] + a.eps);
+    const float o = a.beta ? a.beta[c] : 0.f;
+    const long long base = plane * a.HW;
+    auto f = [&](float v, float s) {
+      float r = fmaf(v - mu, k, o) + s;
+      return a.relu ? fmaxf(r, 0.f) : r;
+    };
+    for (long long i = 4LL * (part * kBnThreads + threadIdx.x); i < hw4; i += 4 * stride) {
+      const float4 v = ld4<VEC>(x, base + i);
+      const float4 s = skip ? ld4<VEC>(skip, base + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      st4<VEC>(y, base + i, make_float4(f(v.x, s.x), f(v.y, s.y), f(v.z, s.z), f(v.w, s.w)));
+    }
+    for (long long i = (long long)hw4 + part * kBnThreads + threadIdx.x; i < a.HW; i += stride)
+      y[base + i] = f(x[base + i], skip ? skip[base + i] : 0.f);
+  }
+}
+
 }  // namespace
 }  // namespace dro
 
@@ -521,4 +581,41 @@ extern "C" int dro_batchnorm_relu_backward(const float* grad_out, const float* x
   else
     hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, ag, dim3(kBnThreads), 0, s, a, g);
   return launch_status("bn_bwd_apply_kernel launch failed");
+}
+
+extern "C" int dro_batchnorm_eval_act(const float* x, const float* gamma, const float* beta,
+                                      const float* running_mean, const float* running_var,
+                                      const float* skip, int relu, int N, int C, int HW, float eps,
+                                      float* y, void* stream) {
+  if (!x || !y || !running_mean || !running_var || (!gamma) != (!beta)) {
+    set_error("batchnorm_eval_act: NULL pointer (x, y, running_mean, running_var; gamma and beta together)");
+    return DRO_E_NULL;
+  }
+  if (N < 1 || C < 1 || HW < 1 || (long long)N * C * HW >= (1LL << 31)) {
+    set_error("batchnorm_eval_act: sizes out of range (N, C, HW >= 1, N * C * HW < 2^31)");
+    return DRO_E_SHAPE;
+  }
+  if (relu != 0 && relu != 1) {
+    set_error("batchnorm_eval_act: relu must be 0 or 1");
+    return DRO_E_MODE;
+  }
+  if (!(eps >= 0.f) || !isfinite(eps)) {
+    set_error("batchnorm_eval_act: eps must be finite and >= 0");
+    return DRO_E_MODE;
+  }
+  BnGeom g;
+  g.N = N;
+  g.C = C;
+  g.HW = HW;
+  g.Q = g.chunk = 0;
+  const int per = apply_blocks(g);
+  const long long items = (long long)N * C * per;
+  BnEvalArgs a{x, gamma, beta, running_mean, running_var, skip, y, relu, eps, C, HW, per, items};
+  const dim3 grid((unsigned)(items < kBnEvalMaxBlocks ? items : kBnEvalMaxBlocks));
+  hipStream_t s = (hipStream_t)stream;
+  if ((HW & 3) == 0 && aligned16(x) && aligned16(y) && aligned16(skip))
+    hipLaunchKernelGGL(bn_eval_kernel<true>, grid, dim3(kBnThreads), 0, s, a);
+  else
+    hipLaunchKernelGGL(bn_eval_kernel<false>, grid, dim3(kBnThreads), 0, s, a);
+  return launch_status("bn_eval_kernel launch failed");
 }

@@ -5,7 +5,7 @@ PyTorch caching allocator and never synchronises, so whole training steps can
 be captured into a hipGraph.
 """
 from .ops import (DEPTH_DISP, DEPTH_INV, DEPTH_METRIC, POSE_EULER, POSE_MATRIX,
-                  batchnorm_act, bilinear_upsample2x, grad_sink, maxpool3x3s2, depth_metrics, depth_metrics_demon,
+                  batchnorm_act, batchnorm_eval_act, bilinear_upsample2x, grad_sink, maxpool3x3s2, depth_metrics, depth_metrics_demon,
                   pose_mean, post_process_inv_depth, clean_depth, fuse_depths, backproject_points, FUSION_OUTSIDE,
                   render_points, RENDER_REJECTED,
                   percentile, colorize, depth_png16_rows,
@@ -20,5 +20,5 @@ __all__ = ["conv2d", "conv2d_strided", "sepconvgru_half", "weight_grad_scope", "
            "clean_depth", "fuse_depths", "backproject_points", "FUSION_OUTSIDE",
            "render_points", "RENDER_REJECTED",
            "percentile", "colorize", "depth_png16_rows",
-           "pose_mean", "batchnorm_act", "grad_sink", "record_bilinear_cells",
+           "pose_mean", "batchnorm_act", "batchnorm_eval_act", "grad_sink", "record_bilinear_cells",
            "POSE_EULER", "POSE_MATRIX", "DEPTH_METRIC", "DEPTH_INV", "DEPTH_DISP"]

@@ -96,6 +96,7 @@ def load():
     _sig(lib.dro_batchnorm_workspace_bytes, I, I, I, restype=Z)
     _sig(lib.dro_batchnorm_relu_forward, P, P, P, P, I, I, I, I, F, F, P, P, P, P, P, P, P, Z, S)
     _sig(lib.dro_batchnorm_relu_backward, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, Z, S)
+    _sig(lib.dro_batchnorm_eval_act, P, P, P, P, P, P, I, I, I, I, F, P, S)
     _sig(lib.dro_conv2d_workspace_bytes, I, I, I, I, I, I, I, restype=Z)
     _sig(lib.dro_conv2d_plan, I, I, I, I, I, I, I, P)
     _sig(lib.dro_conv2d_plan_cin, I, I, I, I, I, I, I, I, P)
@@ -154,6 +155,7 @@ EXPORTED = (
     "dro_resize_rgb8_to_tensor", "dro_color_jitter_rgb8", "dro_resize_rgb8", "dro_rgb8_to_tensor",
     "dro_png_filtered_bytes", "dro_png_decode",
     "dro_batchnorm_workspace_bytes", "dro_batchnorm_relu_forward", "dro_batchnorm_relu_backward",
+    "dro_batchnorm_eval_act",
     "dro_weight_split_bytes", "dro_weight_split",
     "dro_conv2d_workspace_bytes", "dro_conv2d_plan", "dro_conv2d_plan_cin", "dro_conv2d_strided_plan", "dro_debug_conv_stamps", "dro_conv_log", "dro_conv_log_read", "dro_conv2d_forward", "dro_convgru_gates_forward",
     "dro_convgru_blend_forward", "dro_conv2d_backward", "dro_conv2d_backward_gapped", "dro_sum_n",

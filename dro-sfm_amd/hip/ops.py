@@ -1137,6 +1137,56 @@ def batchnorm_act(x, bn, skip=None, relu=True):
         1 if relu else 0, bn.eps, bn.momentum)
 
 
+# ------------------------------------------------------------------ eval-mode BatchNorm (+ skip) (+ ReLU)
+@torch.library.custom_op("dro::batchnorm_eval_act", mutates_args=())
+def _batchnorm_eval_op(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], running_mean: Tensor,
+                       running_var: Tensor, skip: Optional[Tensor], relu: bool, eps: float) -> Tensor:
+    """act(F.batch_norm(x, running_mean, running_var, weight, bias, training=False) + skip), float32 NCHW,
+    one launch (csrc/batchnorm.hip bn_eval_kernel)."""
+    lib = _lib.load()
+    require_device(x, weight, bias, running_mean, running_var, skip, what="batchnorm_eval_act")
+    N, C, H, W = x.shape
+    x = x.contiguous()
+    skip = skip.contiguous() if skip is not None else None
+    y = torch.empty_like(x)
+    check(lib.dro_batchnorm_eval_act(ptr(x), ptr(weight), ptr(bias), ptr(running_mean), ptr(running_var), ptr(skip),
+                                     int(relu), N, C, H * W, float(eps), ptr(y), stream_of(x)),
+          "dro_batchnorm_eval_act")
+    return y
+
+
+@_batchnorm_eval_op.register_fake
+def _(x, weight, bias, running_mean, running_var, skip, relu, eps):
+    return x.new_empty(x.shape)
+
+
+def batchnorm_eval_act(x, bn, skip=None, relu=True):
+    """act(bn(x) + skip) for an eval-mode nn.BatchNorm2d `bn` (float32 NCHW):
+    torch.nn.functional.batch_norm(training=False) on the running statistics,
+    the residual add and the ReLU in one launch (reference
+    networks/optim/extractor.py:7-107 via torchvision's BasicBlock in eval
+    mode).  The statistics and the affine parameters are read by the kernel on
+    every launch: a captured graph follows their in-place updates.  Inference
+    only: no autograd formula.  torch.ops.dro.batchnorm_eval_act."""
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("batchnorm_eval_act: expects a float32 NCHW tensor")
+    if bn.running_mean is None or bn.running_var is None:
+        raise RuntimeError("batchnorm_eval_act: the BatchNorm has no running statistics "
+                           "(track_running_stats=False normalises with batch statistics in eval mode too)")
+    if (bn.weight is None) != (bn.bias is None):
+        raise RuntimeError("batchnorm_eval_act: weight and bias must be given together")
+    if skip is not None and skip.shape != x.shape:
+        raise RuntimeError(f"batchnorm_eval_act: skip {tuple(skip.shape)} does not match x {tuple(x.shape)}")
+    if x.shape[1] != bn.running_mean.numel():
+        raise RuntimeError(f"batchnorm_eval_act: x has {x.shape[1]} channels, the BatchNorm {bn.running_mean.numel()}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, skip, bn.weight, bn.bias)):
+        raise RuntimeError("batchnorm_eval_act: inference only (an input requires grad); call it under "
+                           "torch.no_grad()")
+    w = bn.weight.detach() if bn.weight is not None else None
+    b = bn.bias.detach() if bn.bias is not None else None
+    return torch.ops.dro.batchnorm_eval_act(x, w, b, bn.running_mean, bn.running_var, skip, bool(relu), float(bn.eps))
+
+
 # ------------------------------------------------------------------ depth evaluation metrics
 def crop_rect(crop, H, W):
     """Crop rectangle (y1, y2, x1, x2) of compute_depth_metrics

@@ -20,7 +20,9 @@ with fixed-order fp64 statistics, against 6-9 PyTorch launches per site
 (DRO_BN_FUSION=0|large|all / hip.bnconv.set_bn_fusion: A/B runs).  Not MIOpen's BN: measured on MI355X
 in round 2, its one-pass variance put 1e-2 relative error on encoder gradients
 against the fp64 oracle.  Eval mode and CPU tensors use PyTorch's native
-kernels.
+kernels; with set_fused_eval_batchnorm(True) (default off; InferenceSession
+switches it on) eval-mode BN + skip + ReLU on the GPU is one launch of
+hip.batchnorm_eval_act per site, which reads the running statistics itself.
 The 2x bilinear upsampling of the fusion head is a HIP kernel
 (hip.bilinear_upsample2x): ATen's loops over all planes per output pixel.  So
 is the stem's 3x3/s2 max pooling (hip.maxpool3x3s2, bit-identical to
@@ -38,6 +40,7 @@ stride-2 forward differed run to run by ~1e-6, which the untrained recurrence
 amplified to 2e-4 in the loss).  set_native_strided_convs(False) puts them on
 MIOpen for A/B runs.
 """
+import contextlib
 import os
 
 import torch
@@ -104,6 +107,34 @@ def set_fused_batchnorm(enabled):
     _FUSED_BN[0] = bool(enabled)
 
 
+_FUSED_EVAL_BN = [False]
+
+
+def set_fused_eval_batchnorm(enabled):
+    """hip.batchnorm_eval_act for eval-mode BN (+ skip) (+ ReLU) on the GPU: one
+    launch per site instead of ATen's batch_norm, add and relu (default False:
+    the eval path is then exactly the ATen one).  models.session.InferenceSession
+    switches it on around its forwards.  Returns the previous setting."""
+    prev = _FUSED_EVAL_BN[0]
+    _FUSED_EVAL_BN[0] = bool(enabled)
+    return prev
+
+
+@contextlib.contextmanager
+def fused_eval_batchnorm(enabled=True):
+    """set_fused_eval_batchnorm(enabled) for the duration of a with block; the
+    previous setting is restored on the way out, also after an exception."""
+    prev = set_fused_eval_batchnorm(enabled)
+    try:
+        yield
+    finally:
+        _FUSED_EVAL_BN[0] = prev
+
+
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def _fused_bn_ok(bn, conv, x, stride=1):
     """BN inside the conv launches (hip.bnconv) for this site: the native conv
     engine and the fused BN are on, the conv is 3x3 stride 1 and the site is
@@ -128,6 +159,11 @@ class BatchNorm2d(nn.BatchNorm2d):
             if relu:   # parity tests: the ReLU branch this site took (hip.record_bilinear_cells)
                 hip.ops.record_branch(("relu", getattr(self, "_dro_tag", None)), lambda: (y > 0).to(torch.uint8), x)
             return y
+        if (_FUSED_EVAL_BN[0] and not self.training and x.is_cuda
+                and not _needs_grad(x, skip, self.weight, self.bias)):
+            # eval mode (inference): BN on the running statistics, the skip and
+            # the ReLU in one launch (set_fused_eval_batchnorm, default off)
+            return hip.batchnorm_eval_act(x, self, skip=skip, relu=relu)
         y = self(x)
         if skip is not None:
             y = y + skip

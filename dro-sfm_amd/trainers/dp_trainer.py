@@ -675,7 +675,7 @@ class DataParallelTrainer:
         self.model.train()
         return self._step_inner(batch, **fwd_kw)
 
-    def validate(self, loader, params, demon=False, evaluate=evaluate_depth):
+    def validate(self, loader, params, demon=False, evaluate=evaluate_depth, session=None):
         """One validation epoch (HorovodTrainer.validate -> validation_step ->
         ModelWrapper.evaluate_depth, horovod_trainer.py:129-155 and
         model_wrapper.py:355-399): `evaluate(model, batch, params, demon=demon)`
@@ -689,14 +689,26 @@ class DataParallelTrainer:
         the current stream, in eval mode: parameters, BatchNorm buffers,
         gradients and optimizer state are only read, so it can run between two
         GraphedTrainStep.step calls.  Every rank must see the same metric
-        names (checked)."""
-        modes = [(m, m.training) for m in self.model.modules()]
-        self.model.eval()
+        names (checked).
+
+        `session`: a models.session.InferenceSession over this trainer's model;
+        it is then what `evaluate` receives in place of the model, so the
+        forwards are graph replays (captured on the first call per batch shape,
+        in the session's own memory pool).  The same holds between
+        GraphedTrainStep.step calls: a replay only reads the model, and follows
+        the parameters Adam updated in place."""
+        target = self.model
+        if session is not None:
+            if getattr(session, "model", None) is not self.model:
+                raise RuntimeError("validate: the session must hold this trainer's model")
+            target = session
+        modes = [(m, m.training) for m in target.modules()]
+        target.eval()
         dev = self.grads.flat.device
         names, sums, count = (), None, torch.zeros(1, device=dev)
         try:
             for batch in loader:
-                metrics = evaluate(self.model, batch, params, demon=demon)["metrics"]
+                metrics = evaluate(target, batch, params, demon=demon)["metrics"]
                 if not metrics:
                     continue
                 vals = torch.stack([v.float() for v in metrics.values()])

@@ -494,6 +494,25 @@ int dro_batchnorm_relu_backward(const float* grad_out, const float* x, const flo
                                 float* grad_skip, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* Eval-mode BatchNorm2d fused with the residual add and the ReLU that follow it
+ * in the same encoders: torchvision's BasicBlock in eval mode,
+ * networks/optim/extractor.py:7-107 of the reference.  Replaces
+ * torch.nn.functional.batch_norm(training=False) [+ add] [+ relu] (three ATen
+ * launches and three passes over the activations) by one launch:
+ *   y = act(fmaf(x - running_mean[c], k_c, beta[c]) [+ skip]),
+ *   k_c = gamma[c] / sqrtf(running_var[c] + eps).
+ * The statistics and the affine parameters are read on every launch: nothing
+ * is folded on the host, so a replayed graph follows in-place updates of them.
+ * x, y, skip: NCHW [N, C, HW] fp32; y must not alias x or skip.  gamma and beta
+ * are nullable together (1 and 0), skip is nullable, relu is 0 or 1.
+ * DRO_E_NULL: x, y, running_mean or running_var NULL, or exactly one of gamma /
+ * beta; DRO_E_SHAPE: N, C or HW < 1, or N * C * HW >= 2^31; DRO_E_MODE: relu
+ * not 0 / 1, eps negative or not finite. */
+int dro_batchnorm_eval_act(const float* x, const float* gamma, const float* beta,
+                           const float* running_mean, const float* running_var,
+                           const float* skip, int relu, int N, int C, int HW, float eps,
+                           float* y, void* stream);
+
 /* ------------------------------------------------------------------------
  * Stride-1 'same' convolutions on f32 MFMA for the recurrent update blocks.
  * Replace the nn.Conv2d + activation + torch.cat chains of

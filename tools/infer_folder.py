@@ -2,7 +2,7 @@
 line of the reference's scripts/infer_video.py up to its per-frame outputs.
 
     python tools/infer_folder.py --checkpoint model.ckpt --input frames/ --output out/ \
-        [--image_shape 192 640] [--data_type kitti | --intrinsics FX FY CX CY] [--save npz|png]
+        [--image_shape 192 640] [--data_type kitti | --intrinsics FX FY CX CY] [--save npz|png] [--session]
 
 The frames (sorted by name, one size) are decoded with Pillow, resized on the
 GPU (datasets.gpu_transforms.resize_to_tensor) and run through
@@ -47,6 +47,9 @@ def main():
                     help="the raw frames' camera, instead of --data_type")
     ap.add_argument("--save", choices=["npz", "png"], default=None, help="also write depth files")
     ap.add_argument("--frames_per_forward", type=int, default=4)
+    ap.add_argument("--session", action="store_true",
+                    help="run through models.session.InferenceSession: the forward replayed from a hipGraph, with the "
+                         "fused eval BatchNorm (default: eager)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("infer_folder: needs a ROCm device (there is no CPU path)")
@@ -66,6 +69,9 @@ def main():
     model.add_depth_net(load_network(net, ckpt["state_dict"], ["depth_net", "disp_network"]))
     dev = torch.device("cuda", 0)
     model = model.to(dev)
+    if args.session:
+        from dro_sfm_amd.models.session import InferenceSession
+        model = InferenceSession(model)
     names = sorted(f for f in os.listdir(args.input) if f.lower().endswith((".png", ".jpg", ".jpeg")))
     if len(names) < 3:
         sys.exit("infer_folder: at least 3 frames are needed (each frame is predicted with its two neighbours)")

@@ -3,6 +3,7 @@ line of the reference's scripts/infer_video.py in its point-cloud mode.
 
     python tools/reconstruct_folder.py --checkpoint model.ckpt --input frames/ --output out/ \
         [--ply] [--renders chase|first_person] [--kitti] [--image_shape 192 640] [--intrinsics FX FY CX CY]
+        [--session]
 
 The frames (sorted by name, one size) are decoded with Pillow, resized on the
 GPU and run through models.reconstruct.reconstruct_sequence.  out/pose.obj is
@@ -41,6 +42,9 @@ def main():
     ap.add_argument("--point_size", type=int, default=5)
     ap.add_argument("--no_fusion", action="store_true", help="the reference's output as it stands (fusion disabled)")
     ap.add_argument("--frames_per_forward", type=int, default=4)
+    ap.add_argument("--session", action="store_true",
+                    help="run through models.session.InferenceSession: the forward replayed from a hipGraph, with the "
+                         "fused eval BatchNorm (default: eager)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("reconstruct_folder: needs a ROCm device (there is no CPU path)")
@@ -61,6 +65,9 @@ def main():
     model.add_depth_net(load_network(net, ckpt["state_dict"], ["depth_net", "disp_network"]))
     dev = torch.device("cuda", 0)
     model = model.to(dev)
+    if args.session:
+        from dro_sfm_amd.models.session import InferenceSession
+        model = InferenceSession(model)
     names = sorted(f for f in os.listdir(args.input) if f.lower().endswith((".png", ".jpg", ".jpeg")))
     if len(names) < 3:
         sys.exit("reconstruct_folder: at least 3 frames are needed (each frame is predicted with its two neighbours)")
